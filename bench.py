@@ -25,9 +25,20 @@ wall time.
 itself (torch.distributed.run, 127.0.0.1) before anything touches a GPU;
 under torchrun --gpus must equal WORLD_SIZE.
 
+A plain run sets up, warms up, times its K steps and prints the line (its
+solver statistics and SpMV roofline come from the timed steps themselves).
+--full adds what takes runs of its own: the parity samples against the
+oracle + spsolve, the host-to-host leg, the extra configurations (--legs)
+and the CPU baseline; their fields of the line are null without it.
+--dump-outputs DIR writes the V of the last timed step (or a fixed seeded
+sample of its timesteps) to DIR/V.npy; the synthetic inputs depend on the
+arguments alone, so two builds can be compared output for output.
+
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
                     [--config C3] [--precision mixed|f64] [--precond amg|jacobi]
-                    [--fixed-timesteps T] [--io device|host] [--no-cpu-baseline]
+                    [--fixed-timesteps T] [--io device|host] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--legs F3,S1] [--host-batches H]
+                            [--parity-samples P]]
 """
 from __future__ import annotations
 
@@ -113,7 +124,46 @@ def parse():
     ap.add_argument("--host-batches", type=int, default=4,
                     help="--io device: batches of the host-to-host leg (SURVEY.md 8(d)'s metric) timed after "
                          "the device-resident region (0: none)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the bench measures or checks: the "
+                         "parity samples against the oracle + spsolve, the host-to-host leg, the extra "
+                         "configurations (--legs) and the CPU baseline (each tuned by its own option above); "
+                         "without it a run only sets up, warms up, times its steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the V of the last timed step to DIR/V.npy (float64; "
+                         "a fixed seeded sample of its timesteps when it is larger than 48 MiB) and the "
+                         "timesteps of those rows to DIR/V_timesteps.npy")
+    args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline, args.parity_samples, args.legs, args.host_batches = True, 0, "none", 0
+    return args
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: all ranks' V rows together
+
+
+def dump_outputs(out_dir, rank, world, V, k_first, torch):
+    """--dump-outputs: V (rows, 2N), the last timed call's result as its caller
+    holds it (a device tensor, or the numpy array of --io host), written as
+    float64 to out_dir/V.npy (V_rank<r>.npy with several ranks) with the
+    timestep of every row in V_timesteps.npy. A V larger than this rank's
+    share of DUMP_BYTES is sampled: rows drawn once by a fixed seed, so the
+    same arguments select the same timesteps in every run and build."""
+    rows, width = int(V.shape[0]), int(V.shape[1])
+    cap = max(1, DUMP_BYTES // world // (8 * width))
+    pick = np.arange(rows)
+    if rows > cap:
+        pick = np.sort(np.random.default_rng(20240229).choice(rows, cap, replace=False))
+    if isinstance(V, np.ndarray):
+        out = np.ascontiguousarray(V[pick], dtype=np.float64)
+    else:
+        out = V[torch.from_numpy(pick).to(V.device)].cpu().numpy().astype(np.float64, copy=False)
+    os.makedirs(out_dir, exist_ok=True)
+    tag = "" if world == 1 else "_rank%d" % rank
+    np.save(os.path.join(out_dir, "V%s.npy" % tag), out)
+    np.save(os.path.join(out_dir, "V_timesteps%s.npy" % tag), (k_first + pick).astype(np.float64))
+    return {"V%s.npy" % tag: [len(pick), width], "rows_of_last_step": rows,
+            "rows": "all" if len(pick) == rows else "seeded sample"}
 
 
 def self_launch(args):
@@ -585,6 +635,11 @@ def main():
         agg["max_outer_steps"] = max(agg.get("max_outer_steps", 0), st["outer_steps"])
     sync()
     elapsed = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and not dry and timed_calls:
+        a_, b_ = timed_calls[-1]
+        dumped = dump_outputs(args.dump_outputs, rank, world, kept[-1] if host_io else V_dev[:b_ - a_],
+                              k_off + a_, torch)
     # parity samples: timesteps of the last timed call, its V as the timed
     # solve returned it (V_dev holds the last call's batch; host io: kept[-1])
     samples = []
@@ -703,6 +758,7 @@ def main():
             "parity": parity,
             "legs": legs or None,
             "cpu_baseline": cpu,
+            **({"dump_outputs": dumped} if dumped else {}),
             "solver": {"pcg_iterations_per_timestep": round(agg["iterations"] / n_local, 1),
                        "failed": agg["failed"], "recovered": agg["recovered"],
                        "max_rel_residual": agg["max_rel_residual"],

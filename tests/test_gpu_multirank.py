@@ -32,7 +32,7 @@ def _bench(*argv):
 @pytest.mark.timeout(300)
 def test_two_ranks_weak():
     line = _bench("--gpus", "2", "--config", "C2", "--precision", "mixed", "--steps", "2", "--warmup", "1",
-                  "--batch", "64", "--no-cpu-baseline", "--host-batches", "0")
+                  "--batch", "64", "--full", "--no-cpu-baseline", "--host-batches", "0")
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and "defect" not in line
     assert line["config"]["timesteps_timed"] == 2 * 2 * 64
     assert line["solver"]["failed"] == line["solver"]["recovered"] == 0
@@ -43,7 +43,8 @@ def test_two_ranks_weak():
 @pytest.mark.timeout(300)
 def test_two_ranks_strong_fixed_job():
     line = _bench("--gpus", "2", "--config", "C2", "--precision", "mixed", "--steps", "1", "--warmup", "1",
-                  "--fixed-timesteps", "200", "--batch", "64", "--no-cpu-baseline", "--host-batches", "0")
+                  "--fixed-timesteps", "200", "--batch", "64", "--full", "--no-cpu-baseline",
+                  "--host-batches", "0")
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and "defect" not in line
     assert line["config"]["timesteps_timed"] == 200
     # 100 timesteps per rank in balanced batches: 2 x 50
