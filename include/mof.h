@@ -336,6 +336,28 @@ int mof_cell_areas(const float *points, const int64_t *triangles, int64_t N, int
 int mof_amg_probe(const int32_t *tri, const double *e, int32_t N, int32_t M, int32_t *n_levels,
                   int32_t *level_nodes, double *qtq_err, double *max_curl);
 
+/* Diagnostic (host only, no device): the index tables of the level-0 SELL-64
+ * layout the library would build for this triangle list -- in its internal
+ * vertex order (flags: MOF_NO_REORDER keeps the caller's), symmetric reads
+ * forced on / off by sym = 1 / 0 or decided per mesh (-1). *sell_nb receives
+ * the number of SELL positions; the arrays are optional (call once with them
+ * NULL for the sizes): sell_off (N / 64 rounded up, + 1), col and mir
+ * (*sell_nb each: column; position to read | 1 << 30 if transposed, -1 for
+ * padding) and packed (*sell_nb: one word per position, low half the signed
+ * 16-bit column delta j - i, high half the signed 16-bit delta from the
+ * position itself to the position to read -- 0: own block, otherwise the
+ * transposed twin, -32768: padding; all 0 where the packed path is not taken).
+ * *sym_used: symmetric reads chosen; *packed_used: every delta fits, so the
+ * level-0 row products read the packed words instead of col + mir. */
+int mof_index_probe(const int32_t *tri, int32_t N, int32_t M, uint32_t flags, int32_t sym, int64_t *sell_nb,
+                    int32_t *sell_off, int32_t *col, int32_t *mir, uint32_t *packed, int32_t *sym_used,
+                    int32_t *packed_used);
+/* Test hook (never read from the environment): every mesh and decomposed part
+ * created after mof_test_force_index32(1) keeps the two 32-bit index tables
+ * even where the packed words fit (0: back to the default) -- the packed
+ * path's results are compared with it bit for bit. */
+int mof_test_force_index32(int32_t on);
+
 /* Diagnostic (host only): checks that the XCD-aware workgroup order of the
  * row kernels -- nblk row blocks x batch systems, walked in groups of
  * `group` systems (0: all) -- visits every (row block, system) pair exactly

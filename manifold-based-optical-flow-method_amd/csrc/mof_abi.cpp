@@ -446,6 +446,8 @@ int mof_io_guard(const std::function<void()> &f) { return guarded(f); }
 
 namespace mof {
 
+std::atomic<int> g_force_index32{0};
+
 void mesh_set_own(mof_mesh *m, int32_t nown) {
     MOF_HIP(hipSetDevice(m->device));
     m->n_own = nown;
@@ -464,6 +466,7 @@ void mesh_set_own(mof_mesh *m, int32_t nown) {
             t->nown = nown;
             t->sym = sym;
             t->table = sell_mirror(m->pat, nown, sym, &t->used);
+            if (t->used) t->packed = sell_index_pack(m->pat, t->table);
             if (sh) sh->mirror = t;
             mt = t;
         }
@@ -472,6 +475,12 @@ void mesh_set_own(mof_mesh *m, int32_t nown) {
     const std::vector<int32_t> &mir = mt->table;
     m->sell_mir.alloc(mir.size());
     m->sell_mir.upload(mir.data(), mir.size(), m->stream);
+    // the row products' packed words, beside the mirror table the setup kernels keep reading
+    m->idx_packed = !mt->packed.empty() && !g_force_index32.load();
+    if (m->idx_packed) {
+        m->sell_idx.alloc(mt->packed.size());
+        m->sell_idx.upload(mt->packed.data(), mt->packed.size(), m->stream);
+    }
     int64_t own = 0;  // positions read at their own place: diagonal + upper blocks
     for (int32_t v : mir) own += v >= 0 && !(v & kMirT);
     m->blocks_read = own;
@@ -1158,6 +1167,37 @@ int mof_amg_probe(const int32_t *tri, const double *e, int32_t N, int32_t M, int
             *qtq_err = err;
         }
     });
+}
+
+int mof_index_probe(const int32_t *tri, int32_t N, int32_t M, uint32_t flags, int32_t sym, int64_t *sell_nb,
+                    int32_t *sell_off, int32_t *col, int32_t *mir, uint32_t *packed, int32_t *sym_used,
+                    int32_t *packed_used) {
+    return guarded([&] {
+        MOF_REQUIRE(tri && sell_nb && N > 0 && M > 0, "bad arguments");
+        // the internal order and pattern of mof_mesh_create (host half only;
+        // coordinates play no part in either)
+        mof_mesh m;
+        const std::vector<double> zero(3 * (size_t)std::max(N, M), 0.0);
+        mof::mesh_prepare_host(&m, zero.data(), zero.data(), tri, zero.data(), N, M, flags, nullptr, nullptr);
+        const mof::Pattern &P = m.pat;
+        bool used = false;
+        const std::vector<int32_t> table = mof::sell_mirror(P, N, sym < 0 ? -1 : (sym != 0), &used);
+        const std::vector<uint32_t> pk = used ? mof::sell_index_pack(P, table) : std::vector<uint32_t>();
+        *sell_nb = P.sell_nb();
+        if (sym_used) *sym_used = used;
+        if (packed_used) *packed_used = !pk.empty();
+        if (sell_off) std::copy(P.sell_off.begin(), P.sell_off.end(), sell_off);
+        if (col) std::copy(P.sell_col.begin(), P.sell_col.end(), col);
+        if (mir) std::copy(table.begin(), table.end(), mir);
+        if (packed) {
+            std::fill(packed, packed + P.sell_nb(), 0u);
+            std::copy(pk.begin(), pk.end(), packed);
+        }
+    });
+}
+
+int mof_test_force_index32(int32_t on) {
+    return guarded([&] { mof::g_force_index32.store(on != 0); });
 }
 
 int mof_xcd_map_check(int32_t nblk, int32_t batch, int32_t group) {

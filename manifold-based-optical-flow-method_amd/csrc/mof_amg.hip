@@ -1589,8 +1589,10 @@ __global__ __launch_bounds__(kSubWG) void k_subcycle(SubArgs a) {
 // member position of each vertex; PCG row layout. NS systems per thread sharing the row's column / mirror loads:
 // grid over (row block, system group of NS) in the XCD order (round 2: 916
 // -> 829 us per 512-system launch at NS = 2; 4 lowered the occupancy).
+// PK: the packed index words (kIxPack) instead of the run-time choice between
+// the plain and the mirrored 32-bit tables; the launcher picks the instance.
 constexpr int kRes0NS = 2, kRes0U = kSweepU;
-template <int NS>
+template <int NS, bool PK>
 __global__ __launch_bounds__(kWG) MOF_ROW_OCC void k_res0_ns(int32_t N, int32_t nblk, int32_t B, SysMap sm, MatH mat,
                                                  const float *__restrict__ rv, const float *__restrict__ xv,
                                                  const int32_t *__restrict__ apos,
@@ -1615,10 +1617,12 @@ __global__ __launch_bounds__(kWG) MOF_ROW_OCC void k_res0_ns(int32_t N, int32_t 
         if (i >= N) break;
         float y[NS][2];
         auto xl = [&](int t, int32_t j) { return ld_x0(xv, (int64_t)bs[t] * N + j); };
-        if (mat.sell_mir)
-            spmv_row_hx_ns<true, NS, kRes0U>(mat, bs, i, xl, y);
+        if constexpr (PK)
+            spmv_row_hx_ns<kIxPack, NS, kRes0U>(mat, bs, i, xl, y);
+        else if (mat.sell_mir)
+            spmv_row_hx_ns<kIxMir, NS, kRes0U>(mat, bs, i, xl, y);
         else
-            spmv_row_hx_ns<false, NS, kRes0U>(mat, bs, i, xl, y);
+            spmv_row_hx_ns<kIxPlain, NS, kRes0U>(mat, bs, i, xl, y);
 #pragma unroll
         for (int t = 0; t < NS; ++t) {
             if (!act[t]) continue;
@@ -1635,7 +1639,7 @@ __global__ __launch_bounds__(kWG) MOF_ROW_OCC void k_res0_ns(int32_t N, int32_t 
 // per load batch to keep the waves (round 2: 918 -> 864 us per 512-system
 // launch; 8 slots per batch 1030 us). D^-1 from the row's own diagonal block.
 constexpr int kPost0NS = 2, kPost0U = 4;
-template <int XM, bool ZH, int NS>
+template <int XM, bool ZH, int NS, bool PK>
 __global__ __launch_bounds__(kWG) MOF_ROW_OCC void k_post0_ns(int32_t N, int32_t nblk, int32_t B, SysMap sm, MatH mat,
                                                   const float *__restrict__ rv,
                                                   const float *__restrict__ xv, float omega,
@@ -1673,10 +1677,12 @@ __global__ __launch_bounds__(kWG) MOF_ROW_OCC void k_post0_ns(int32_t N, int32_t
             else
                 return ld_x0(xv, vj);
         };
-        if (mat.sell_mir)
-            spmv_row_hx_ns<true, NS, kPost0U>(mat, bs, i, xl, y, dg);
+        if constexpr (PK)
+            spmv_row_hx_ns<kIxPack, NS, kPost0U>(mat, bs, i, xl, y, dg);
+        else if (mat.sell_mir)
+            spmv_row_hx_ns<kIxMir, NS, kPost0U>(mat, bs, i, xl, y, dg);
         else
-            spmv_row_hx_ns<false, NS, kPost0U>(mat, bs, i, xl, y, dg);
+            spmv_row_hx_ns<kIxPlain, NS, kPost0U>(mat, bs, i, xl, y, dg);
 #pragma unroll
         for (int t = 0; t < NS; ++t) {
             const int64_t vb = (int64_t)bs[t] * N;
@@ -1836,9 +1842,12 @@ void launch_bsweep(const AmgDevice &G, SysMap sm, const float *rv, float *xv, fl
 }
 
 template <int XM, bool ZH, typename... Args>
-void launch_post0(int32_t nblk, int32_t B, hipStream_t s, Args... args) {
+void launch_post0(bool packed, int32_t nblk, int32_t B, hipStream_t s, Args... args) {
     const dim3 g(xcd_grid(nblk, (B + kPost0NS - 1) / kPost0NS, kGrpSmooth > kPost0NS ? kGrpSmooth / kPost0NS : 1));
-    k_post0_ns<XM, ZH, kPost0NS><<<g, kWG, 0, s>>>(args...);
+    if (packed)
+        k_post0_ns<XM, ZH, kPost0NS, true><<<g, kWG, 0, s>>>(args...);
+    else
+        k_post0_ns<XM, ZH, kPost0NS, false><<<g, kWG, 0, s>>>(args...);
 }
 
 inline dim3 grid2(int64_t n, int32_t B) { return dim3((unsigned)((n + kWG - 1) / kWG), (unsigned)B); }
@@ -1849,6 +1858,7 @@ MatH level0_mat(mof_mesh *m) {
     mt.sell_off = m->sell_off.p;
     mt.sell_col = m->sell_col.p;
     mt.sell_mir = m->sym_reads ? m->sell_mir.p : nullptr;
+    mt.sell_idx = m->sym_reads && m->idx_packed ? m->sell_idx.p : nullptr;
     mt.vptr = m->sym_reads ? nullptr : m->vptr.p;
     mt.A = reinterpret_cast<const uint2 *>(m->amg->A0h.p);
     return mt;
@@ -2503,10 +2513,9 @@ void amg_vcycle(mof_mesh *m, int32_t B, const float *r0, float *z0, double *part
         const int32_t smooth = l + 1 < L - 1;
         if (l == 0) {
             if (G.bsw_n > 0) launch_bsweep<false>(G, sm, r0, v[0].x, om, sysi, s);
-            k_res0_ns<kRes0NS><<<dim3(xcd_grid(nblk, (nL + kRes0NS - 1) / kRes0NS,
-                                               kGrpSmooth > kRes0NS ? kGrpSmooth / kRes0NS : 1)),
-                                 kWG, 0, s>>>(v[0].n, nblk, B, sm, mat0, r0, v[0].x,
-                                              G.lv[0].smoothed ? nullptr : v[0].apos, sysi, v[0].r);
+            const dim3 gr(xcd_grid(nblk, (nL + kRes0NS - 1) / kRes0NS, kGrpSmooth > kRes0NS ? kGrpSmooth / kRes0NS : 1));
+            (mat0.sell_idx ? k_res0_ns<kRes0NS, true> : k_res0_ns<kRes0NS, false>)<<<gr, kWG, 0, s>>>(
+                v[0].n, nblk, B, sm, mat0, r0, v[0].x, G.lv[0].smoothed ? nullptr : v[0].apos, sysi, v[0].r);
             if (G.lv[0].smoothed) {
                 k_restrict0_sa<2><<<dim3(xcd_grid(G.lv[0].ngrp, (nL + kNSR - 1) / kNSR, kGrpRestr)), kWG, 0, s>>>(
                     v[0], v[1], G.lv[0].rgrp.p, G.lv[0].ngrp, B, smooth, om1, sysi);
@@ -2541,9 +2550,9 @@ void amg_vcycle(mof_mesh *m, int32_t B, const float *r0, float *z0, double *part
                     k_prolong0<2><<<gp, kWG, 0, s>>>(v[0], v[1], nb0p, B, sysi);
                 if (G.bsw_n > 0) launch_bsweep<true>(G, sm, r0, v[0].y, om, sysi, s);
                 if (zh)
-                    launch_post0<2, true>(nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, v[0].y, om, sysi, z0, part_slot, rd);
+                    launch_post0<2, true>(mat0.sell_idx != nullptr, nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, v[0].y, om, sysi, z0, part_slot, rd);
                 else
-                    launch_post0<2, false>(nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, v[0].y, om, sysi, z0, part_slot, rd);
+                    launch_post0<2, false>(mat0.sell_idx != nullptr, nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, v[0].y, om, sysi, z0, part_slot, rd);
             } else {
                 if (G.lv[0].smoothed)
                     k_prolong0_sa<1><<<gsa, kWG, 0, s>>>(v[0], v[1], nb0, B, sysi);
@@ -2551,9 +2560,9 @@ void amg_vcycle(mof_mesh *m, int32_t B, const float *r0, float *z0, double *part
                     k_prolong0<1><<<gp, kWG, 0, s>>>(v[0], v[1], nb0p, B, sysi);
                 if (G.bsw_n > 0) launch_bsweep<false>(G, sm, r0, v[0].x, om, sysi, s);
                 if (zh)
-                    launch_post0<1, true>(nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, v[0].x, om, sysi, z0, part_slot, rd);
+                    launch_post0<1, true>(mat0.sell_idx != nullptr, nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, v[0].x, om, sysi, z0, part_slot, rd);
                 else
-                    launch_post0<1, false>(nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, v[0].x, om, sysi, z0, part_slot, rd);
+                    launch_post0<1, false>(mat0.sell_idx != nullptr, nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, v[0].x, om, sysi, z0, part_slot, rd);
             }
         }
     }

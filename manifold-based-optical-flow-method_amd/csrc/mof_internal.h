@@ -16,6 +16,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
 #include <cstdlib>
 #include <functional>
@@ -23,6 +24,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mof.h"
@@ -93,6 +95,15 @@ __host__ __device__ inline int32_t sell_block(int32_t slot, int32_t td) {
 // sell_mirror entries: position | kMirT = read the block transposed
 constexpr int32_t kMirT = 1 << 30;
 constexpr int32_t kMirPos = kMirT - 1;
+// The packed index word of a SELL position (sell_index_pack; read by the
+// level-0 row products, mof_rowkern.h kIxPack): low half the signed column
+// delta j - i, high half the signed delta from the position itself to the
+// position to read -- 0: the own block, untransposed; anything else: the
+// transposed twin (a kMirT entry always points at another row); kIdxPad:
+// padding (read the row's diagonal, masked).
+constexpr int32_t kIdxPad = -32768;
+// every block position of the packed path is a 32-bit byte offset (16 B fp32 blocks)
+constexpr int64_t kIdxMaxNb = (int64_t)1 << 28;
 
 // Host-side sparsity structures, built once per mesh (mof_pattern.cpp).
 struct Pattern {
@@ -126,6 +137,12 @@ void build_pattern(const int32_t *tri, int32_t N, int32_t M, Pattern &pat,
                    const int32_t *torder = nullptr);
 std::vector<int32_t> rcm_order(const Pattern &pat);
 std::vector<int32_t> sell_mirror(const Pattern &pat, int32_t nown, int sym, bool *used);
+// The packed index words of sell_col and a mirror table of sell_mirror, or
+// empty where a delta does not fit its 16 bits (the mesh or part then keeps
+// the two 32-bit tables).
+std::vector<uint32_t> sell_index_pack(const Pattern &pat, const std::vector<int32_t> &mir);
+// tests only (mof_test_force_index32): every mesh set up from now on keeps the 32-bit tables
+extern std::atomic<int> g_force_index32;
 
 // Per-batch device workspace (capacity B systems).
 struct Workspace {
@@ -194,6 +211,7 @@ struct MirrorTable {
     int sym = -1;
     bool used = false;
     std::vector<int32_t> table;
+    std::vector<uint32_t> packed;  // sell_index_pack(table) with symmetric reads, or empty
 };
 struct MeshShared {
     std::vector<int32_t> tri_new, tri_old, icol;
@@ -248,6 +266,11 @@ struct mof_mesh {
     mof::DevArray<int32_t> sell_mir;  // sell_mirror(pat, n_own): (re)uploaded by mesh_set_own
     int64_t blocks_read = 0;          // blocks an fp32 / bf16 operator pass reads per system
     bool sym_reads = false;           // the mirror table transposes lower blocks
+    // the packed index words the level-0 row products read instead of
+    // sell_col + sell_mir (symmetric reads whose deltas fit); the setup
+    // kernels keep the 32-bit tables
+    mof::DevArray<uint32_t> sell_idx;
+    bool idx_packed = false;
     mof::DevArray<double> e, gw, iw, area, a2;  // a2: [sell_nb][4] (unscaled, bit-exact)
     // operator copies: lambda*a2 (cached per lambda) and A_T/12 with a zero slot M
     mof::DevArray<double> a2s64, w12_64;

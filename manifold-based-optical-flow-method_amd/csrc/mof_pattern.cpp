@@ -239,6 +239,37 @@ std::vector<int32_t> sell_mirror(const Pattern &pat, int32_t nown, int sym, bool
     return mir;
 }
 
+// One index word per SELL position for the level-0 row products (kIdxPad,
+// mof_internal.h): the column is the row plus a small delta (the RCM
+// bandwidth) and the mirror entry the position itself or the transposed
+// twin's a few thousand positions away, so both fit 16 signed bits on the
+// RCM-ordered meshes (C3: |dcol| <= about 1,200). Positions past row N - 1 of
+// the last slice are padding. Empty where a delta does not fit or a block
+// position would not be a 32-bit byte offset.
+std::vector<uint32_t> sell_index_pack(const Pattern &pat, const std::vector<int32_t> &mir) {
+    const int64_t snb = pat.sell_off[pat.nslices];
+    if (snb >= kIdxMaxNb || (int64_t)mir.size() != snb) return {};
+    std::vector<uint32_t> out((size_t)snb, (uint32_t)(uint16_t)kIdxPad << 16);
+    for (int32_t s = 0; s < pat.nslices; ++s) {
+        const int32_t w = (pat.sell_off[s + 1] - pat.sell_off[s]) / kSlice;
+        for (int32_t l = 0; l < kSlice; ++l) {
+            const int32_t i = s * kSlice + l;
+            if (i >= pat.N) break;
+            for (int32_t t = 0; t < w; ++t) {
+                const int64_t pos = pat.sell_off[s] + (int64_t)t * kSlice + l;
+                if (mir[pos] < 0) continue;  // padding
+                const int64_t dcol = (int64_t)pat.sell_col[pos] - i;
+                const int64_t dpos = (int64_t)(mir[pos] & kMirPos) - pos;
+                const bool tr = (mir[pos] & kMirT) != 0;
+                // a transposed read is another row's position, an own read the position itself
+                if (dcol < -32768 || dcol > 32767 || dpos <= kIdxPad || dpos > 32767 || tr != (dpos != 0)) return {};
+                out[pos] = (uint32_t)(uint16_t)(int16_t)dcol | ((uint32_t)(uint16_t)(int16_t)dpos << 16);
+            }
+        }
+    }
+    return out;
+}
+
 // Reverse Cuthill-McKee order of the vertex graph in `pat` (adjacency
 // only). Returns perm with perm[old] = new. BFS from a pseudo-peripheral
 // vertex of every connected component, neighbours in increasing degree,

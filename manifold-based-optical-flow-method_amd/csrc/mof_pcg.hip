@@ -543,7 +543,9 @@ __global__ __launch_bounds__(kWG) void k_pcg_tol(PcgArgs<V> a, double rtol, doub
     pcg_tol_sys<V>(a, rtol, outer_rtol, etol, blockIdx.x);
 }
 
-template <typename V, bool FIRST, bool ZH = false, int NQ = 1>
+// PK: the packed index words (mof_rowkern.h kIxPack; fp32 only) instead of
+// the run-time choice between the plain and the mirrored 32-bit tables
+template <typename V, bool FIRST, bool ZH = false, int NQ = 1, bool PK = false>
 __device__ __forceinline__ void pcg_spmv_rows(const PcgArgs<V> &a, int32_t it, int32_t flags, int32_t rb, int32_t b) {
     constexpr int NT = kWG, RPT = kRows;  // rows per thread
     __shared__ double lds[NQ * (NT / 64)];
@@ -623,13 +625,15 @@ __device__ __forceinline__ void pcg_spmv_rows(const PcgArgs<V> &a, int32_t it, i
         V y0, y1;
         const int64_t vi = vb + i;
         V2 zi;
+        const V *zb = ZH ? reinterpret_cast<const V *>(reinterpret_cast<const uint32_t *>(a.z) + vb) : a.z + 2 * vb;
+        if constexpr (PK)
+            spmv_row_t<kIxPack, V, ZH>(a.mat, b, i, zb, y0, y1);
+        else
+            spmv_row<V, ZH>(a.mat, b, i, zb, y0, y1);
         if constexpr (ZH) {
-            spmv_row<V, true>(a.mat, b, i, reinterpret_cast<const V *>(reinterpret_cast<const uint32_t *>(a.z) + vb),
-                              y0, y1);
             const uint32_t h = reinterpret_cast<const uint32_t *>(a.z)[vi];
             zi = V2{bf16_lo(h), bf16_hi(h)};
         } else {
-            spmv_row<V>(a.mat, b, i, a.z + 2 * vb, y0, y1);
             zi = *reinterpret_cast<const V2 *>(a.z + 2 * vi);
         }
         V2 qi, pi;
@@ -639,13 +643,35 @@ __device__ __forceinline__ void pcg_spmv_rows(const PcgArgs<V> &a, int32_t it, i
         } else {
             const V2 q0 = *reinterpret_cast<const V2 *>(a.q + 2 * vi);
             const V2 p0 = *reinterpret_cast<const V2 *>(a.p + 2 * vi);
-            qi = V2{y0 + beta * q0.x, y1 + beta * q0.y};
-            pi = V2{zi.x + beta * p0.x, zi.y + beta * p0.y};
-            if (!force) {
-                V2 xi = *reinterpret_cast<const V2 *>(a.x + 2 * vi);
-                xi.x += alpha_prev * p0.x;
-                xi.y += alpha_prev * p0.y;
-                *reinterpret_cast<V2 *>(a.x + 2 * vi) = xi;
+            if constexpr (PK) {
+                // Contraction of these updates is the code generator's choice
+                // in the 32-bit instances, and it depends on the row product
+                // before them: p and x fused, q = y + beta q fused with an
+                // fp32 z and left as a product and a sum with a bf16 z (gfx950
+                // ISA of k_pcg_spmv<float, false, ZH>). The packed instances
+                // state that rounding, so a system's bits do not depend on its
+                // index source (tests/test_gpu_index_word.py).
+#pragma clang fp contract(off)
+                if constexpr (ZH)
+                    qi = V2{y0 + beta * q0.x, y1 + beta * q0.y};
+                else
+                    qi = V2{fmaf(beta, q0.x, y0), fmaf(beta, q0.y, y1)};
+                pi = V2{fmaf(beta, p0.x, zi.x), fmaf(beta, p0.y, zi.y)};
+                if (!force) {
+                    V2 xi = *reinterpret_cast<const V2 *>(a.x + 2 * vi);
+                    xi.x = fmaf(alpha_prev, p0.x, xi.x);
+                    xi.y = fmaf(alpha_prev, p0.y, xi.y);
+                    *reinterpret_cast<V2 *>(a.x + 2 * vi) = xi;
+                }
+            } else {
+                qi = V2{y0 + beta * q0.x, y1 + beta * q0.y};
+                pi = V2{zi.x + beta * p0.x, zi.y + beta * p0.y};
+                if (!force) {
+                    V2 xi = *reinterpret_cast<const V2 *>(a.x + 2 * vi);
+                    xi.x += alpha_prev * p0.x;
+                    xi.y += alpha_prev * p0.y;
+                    *reinterpret_cast<V2 *>(a.x + 2 * vi) = xi;
+                }
             }
         }
         *reinterpret_cast<V2 *>(a.q + 2 * vi) = qi;
@@ -656,11 +682,11 @@ __device__ __forceinline__ void pcg_spmv_rows(const PcgArgs<V> &a, int32_t it, i
     block_sum_q<1, NQ>(v, lds);
     if (tid == 0 && rb < a.nblk) a.part_pq[(it & 1) * pqs + red_rec(a.red, a.B, b, rb)] = v[0];
 }
-template <typename V, bool FIRST, bool ZH = false>
+template <typename V, bool FIRST, bool ZH = false, bool PK = false>
 __device__ __forceinline__ void pcg_spmv_body(const PcgArgs<V> &a, int32_t it, int32_t flags) {
     int32_t rb, bl;
     if (!xcd_map(a.nblk, a.sm.n, rb, bl, kGrpSpmv)) return;
-    pcg_spmv_rows<V, FIRST, ZH>(a, it, flags, rb, sm_b(a.sm, bl));
+    pcg_spmv_rows<V, FIRST, ZH, 1, PK>(a, it, flags, rb, sm_b(a.sm, bl));
 }
 
 // Measured and not kept (round 2, profiles/r02_ab/spmvns_*): two systems
@@ -670,23 +696,28 @@ __device__ __forceinline__ void pcg_spmv_body(const PcgArgs<V> &a, int32_t it, i
 // rows of a row block at once (1614 -> 2890 us: one workgroup per CU).
 // the fp32 instances run at >= 5 waves per SIMD (MOF_ROW_OCC: +1 % at C3);
 // the fp64 ones keep the compiler's choice (the hint costs C2 fp64 2.7 %)
-template <typename V, bool FIRST, bool ZH = false>
+template <typename V, bool FIRST, bool ZH = false, bool PK = false>
 __global__ __launch_bounds__(kWG) void k_pcg_spmv(PcgArgs<V> a, int32_t it, int32_t flags) {
-    // bf16 z exists for the fp32 inner solve only (the float specialisations)
-    static_assert(!ZH || sizeof(V) == 4, "bf16 z needs the fp32 SpMV");
-    pcg_spmv_body<V, FIRST, ZH>(a, it, flags);
+    // bf16 z and the packed index words exist for the fp32 inner solve only
+    // (the float specialisations)
+    static_assert((!ZH && !PK) || sizeof(V) == 4, "bf16 z and packed indices need the fp32 SpMV");
+    pcg_spmv_body<V, FIRST, ZH, PK>(a, it, flags);
 }
-#define MOF_SPMV_F32(FIRST, ZH)                                                                              \
+#define MOF_SPMV_F32(FIRST, ZH, PK)                                                                          \
     template <>                                                                                              \
-    __global__ __launch_bounds__(kWG) MOF_ROW_OCC void k_pcg_spmv<float, FIRST, ZH>(PcgArgs<float> a,       \
-                                                                                   int32_t it,              \
-                                                                                   int32_t flags) {         \
-        pcg_spmv_body<float, FIRST, ZH>(a, it, flags);                                                       \
+    __global__ __launch_bounds__(kWG) MOF_ROW_OCC void k_pcg_spmv<float, FIRST, ZH, PK>(PcgArgs<float> a,   \
+                                                                                       int32_t it,          \
+                                                                                       int32_t flags) {     \
+        pcg_spmv_body<float, FIRST, ZH, PK>(a, it, flags);                                                   \
     }
-MOF_SPMV_F32(true, false)
-MOF_SPMV_F32(false, false)
-MOF_SPMV_F32(true, true)
-MOF_SPMV_F32(false, true)
+MOF_SPMV_F32(true, false, false)
+MOF_SPMV_F32(false, false, false)
+MOF_SPMV_F32(true, true, false)
+MOF_SPMV_F32(false, true, false)
+MOF_SPMV_F32(true, false, true)
+MOF_SPMV_F32(false, false, true)
+MOF_SPMV_F32(true, true, true)
+MOF_SPMV_F32(false, true, true)
 #undef MOF_SPMV_F32
 // workgroup size of an SpMV launch
 template <typename V>
@@ -696,22 +727,21 @@ template <typename V>
 dim3 spmv_grid(const PcgArgs<V> &a) {
     return dim3(xcd_grid(a.nblk, a.sm.n, kGrpSpmv));
 }
+// the SpMV instance of a launch: first iteration or not, bf16 z, packed index words
+template <typename V>
+auto spmv_kernel(const PcgArgs<V> &a, bool first) -> void (*)(PcgArgs<V>, int32_t, int32_t) {
+    if constexpr (sizeof(V) == 4) {
+        if (a.mat.sell_idx) {
+            if (a.zh) return first ? k_pcg_spmv<V, true, true, true> : k_pcg_spmv<V, false, true, true>;
+            return first ? k_pcg_spmv<V, true, false, true> : k_pcg_spmv<V, false, false, true>;
+        }
+        if (a.zh) return first ? k_pcg_spmv<V, true, true> : k_pcg_spmv<V, false, true>;
+    }
+    return first ? k_pcg_spmv<V, true, false> : k_pcg_spmv<V, false, false>;
+}
 template <typename V>
 void launch_spmv(const PcgArgs<V> &a, bool first, dim3, hipStream_t s, int32_t it, int32_t flags) {
-    const dim3 g = spmv_grid(a);
-    constexpr bool zh_ok = sizeof(V) == 4;
-    if (zh_ok && a.zh) {
-        if constexpr (zh_ok) {
-            if (first)
-                k_pcg_spmv<V, true, true><<<g, spmv_wg<V>(), 0, s>>>(a, it, flags);
-            else
-                k_pcg_spmv<V, false, true><<<g, spmv_wg<V>(), 0, s>>>(a, it, flags);
-        }
-    } else if (first) {
-        k_pcg_spmv<V, true, false><<<g, spmv_wg<V>(), 0, s>>>(a, it, flags);
-    } else {
-        k_pcg_spmv<V, false, false><<<g, spmv_wg<V>(), 0, s>>>(a, it, flags);
-    }
+    spmv_kernel(a, first)<<<spmv_grid(a), spmv_wg<V>(), 0, s>>>(a, it, flags);
 }
 
 constexpr int kUpdRB = 4;  // row blocks per update workgroup
@@ -1126,6 +1156,7 @@ MatArgs<V> make_mat(mof_mesh *m, const V *A) {
     mt.sell_off = m->sell_off.p;
     mt.sell_col = m->sell_col.p;
     mt.sell_mir = m->sym_reads ? m->sell_mir.p : nullptr;
+    mt.sell_idx = sizeof(V) == 4 && m->sym_reads && m->idx_packed ? m->sell_idx.p : nullptr;
     mt.vptr = m->sym_reads ? nullptr : m->vptr.p;
     mt.A = A;
     return mt;
@@ -1331,10 +1362,7 @@ int64_t pcg(mof_mesh *m, int32_t B, const MatArgs<V> &mat, const V *dinv, const 
                 // events stamped by the kernel's own dispatch packet (start
                 // and end of its execution, as rocprof's kernel trace), not
                 // separate marker packets around it
-                constexpr bool zh_ok = sizeof(V) == 4;
-                auto kf = it == 0 ? (zh_ok && a.zh ? k_pcg_spmv<V, true, zh_ok> : k_pcg_spmv<V, true, false>)
-                                  : (zh_ok && a.zh ? k_pcg_spmv<V, false, zh_ok> : k_pcg_spmv<V, false, false>);
-                hipExtLaunchKernelGGL(kf, spmv_grid(a), dim3(spmv_wg<V>()), 0, s, ev[2 * c], ev[2 * c + 1], 0, a, it, 0);
+                hipExtLaunchKernelGGL(spmv_kernel(a, it == 0), spmv_grid(a), dim3(spmv_wg<V>()), 0, s, ev[2 * c], ev[2 * c + 1], 0, a, it, 0);
             } else {
                 launch_spmv(a, it == 0, gx, s, it, 0);
             }
@@ -2052,7 +2080,7 @@ double bench_spmv(mof_mesh *m, uint32_t precision, int32_t B, int32_t reps, hipS
     auto launch = [&]() {
         if (precision == MOF_PREC_MIXED) {
             PcgArgs<float> a = make_args<float>(m, B, make_mat<float>(m, w.A32.p), w.dinv32.p);
-            k_pcg_spmv<float, false><<<spmv_grid(a), spmv_wg<float>(), 0, s>>>(a, 1, kForce);
+            spmv_kernel(a, false)<<<spmv_grid(a), spmv_wg<float>(), 0, s>>>(a, 1, kForce);
         } else {
             PcgArgs<double> a = make_args<double>(m, B, make_mat<double>(m, w.A64.p), w.dinv64.p);
             k_pcg_spmv<double, false><<<gx, spmv_wg<double>(), 0, s>>>(a, 1, kForce);

@@ -206,6 +206,7 @@ struct MatArgs {
     int64_t sell_nb;
     const int32_t *sell_off, *sell_col;
     const int32_t *sell_mir;  // mirror table (symmetric reads), or null
+    const uint32_t *sell_idx; // packed index words (kIxPack; sell_index_pack), or null
     const int32_t *vptr;      // plain reads: the adjacency row pointers (row i holds
                               // vptr[i+1] - vptr[i] blocks), or null (slice width)
     const V *A;  // [B][sell_nb][4]
@@ -234,6 +235,37 @@ __device__ __forceinline__ typename VT<V>::V2 ld2(const V *p) {
     return *reinterpret_cast<const typename VT<V>::V2 *>(p);
 }
 
+// Where a row product takes its columns and block positions from (a template
+// choice of the row products; the launchers pick the kernel instance):
+//  kIxPlain  sell_col, every block at its own position;
+//  kIxMir    sell_col and the 32-bit mirror table, two loads per slot;
+//  kIxPack   one packed word per slot (sell_index_pack, mof_pattern.cpp):
+//            the column and the position as 16-bit deltas from the row and
+//            from the slot's own position -- half the index bytes, one load
+//            and one address per slot, 32-bit position arithmetic on the
+//            system's base pointer (the packed path holds 16 sell_nb < 2^32).
+constexpr int kIxPlain = 0, kIxMir = 1, kIxPack = 2;
+__device__ __forceinline__ int32_t idx_dcol(uint32_t w) { return (int32_t)(w << 16) >> 16; }
+__device__ __forceinline__ int32_t idx_dpos(uint32_t w) { return (int32_t)w >> 16; }
+
+// The SELL slice of row i as a scalar: the 64 rows of a wave are one slice
+// (every row kernel's wave covers 64 consecutive rows from a multiple of 64,
+// and lanes past N have left or are clamped to N - 1, which lies in the same
+// slice or is the row of every lane), so sell_off[s], sell_off[s + 1] become
+// one scalar load instead of a vector load that every address of the wave
+// waits for.
+__device__ __forceinline__ int32_t wave_slice(int32_t i) { return __builtin_amdgcn_readfirstlane(i >> 6); }
+
+template <typename T>
+__device__ __forceinline__ const T *byte_off(const T *base, uint32_t bytes) {
+    return reinterpret_cast<const T *>(reinterpret_cast<const char *>(base) + bytes);
+}
+__device__ __forceinline__ void ld_blk32(const float *A, uint32_t pos, float (&a)[4]) {
+    const float4 v = *byte_off(reinterpret_cast<const float4 *>(A), pos * 16u);
+    a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w;
+}
+__device__ __forceinline__ void ld_blk32(const double *A, uint32_t pos, double (&a)[4]) { ld_blk(A, (int64_t)pos, a); }
+
 // y_i = sum_t A_blk(i,t) x_col(i,t) over the SELL-64 row of vertex i.
 // Slots are processed U at a time with every load of a chunk issued before
 // the first use (column indices, then block values, then the x gathers), so
@@ -248,7 +280,7 @@ constexpr int kSpmvU = 8, kSweepU = 8;
 
 // ZH: the operand is a bf16 pair per row (uint32 each; x points at the
 // system's first one) instead of V2
-template <bool sym, typename V, bool ZH = false>
+template <int IX, typename V, bool ZH = false>
 __device__ __forceinline__ void spmv_row_t(const MatArgs<V> &mt, int32_t b, int32_t i,
                                            const V *__restrict__ x, V &y0, V &y1) {
     // no fp contraction: the symmetric and the plain instance must round
@@ -257,26 +289,35 @@ __device__ __forceinline__ void spmv_row_t(const MatArgs<V> &mt, int32_t b, int3
 #pragma clang fp contract(off)
     using V2 = typename VT<V>::V2;
     constexpr int U = kSpmvU;  // fp64: 525 vs 536 us per C2 launch with 4
+    constexpr bool sym = IX != kIxPlain;
     const V *A = mt.A + 4 * (int64_t)b * mt.sell_nb;
-    const int32_t s = i >> 6, l = i & 63;
+    const int32_t s = wave_slice(i), l = i & 63;
     const int32_t o = mt.sell_off[s];
     const int32_t w = (mt.sell_off[s + 1] - o) >> 6;
     const int32_t wl = sym ? w : row_width(mt.vptr, i, w);  // this row's slots
     V a0 = 0, a1 = 0;
     for (int32_t t0 = 0; t0 < w; t0 += U) {
-        int32_t j[U], mr[U];
+        int32_t j[U], mr[U];  // kIxPack: mr = the word's position delta
         V blk[U][4];
         V2 xj[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int32_t t = min(t0 + u, wl - 1);
-            j[u] = mt.sell_col[(int64_t)o + t * kSlice + l];
-            if constexpr (sym) mr[u] = mt.sell_mir[(int64_t)o + t * kSlice + l];
+            if constexpr (IX == kIxPack) {
+                const uint32_t iw = *byte_off(mt.sell_idx, (uint32_t)(o + t * kSlice + l) * 4u);
+                j[u] = i + idx_dcol(iw);
+                mr[u] = idx_dpos(iw);
+            } else {
+                j[u] = mt.sell_col[(int64_t)o + t * kSlice + l];
+                if constexpr (sym) mr[u] = mt.sell_mir[(int64_t)o + t * kSlice + l];
+            }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int32_t t = min(t0 + u, wl - 1);
-            if constexpr (sym)
+            if constexpr (IX == kIxPack)
+                ld_blk32(A, (uint32_t)(mr[u] == kIdxPad ? o + l : o + t * kSlice + l + mr[u]), blk[u]);
+            else if constexpr (sym)
                 ld_blk(A, mir_pos(mr[u], (int64_t)o + l), blk[u]);
             else
                 ld_blk(A, (int64_t)o + t * kSlice + l, blk[u]);
@@ -293,8 +334,14 @@ __device__ __forceinline__ void spmv_row_t(const MatArgs<V> &mt, int32_t b, int3
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if constexpr (sym) {
-                const bool on = t0 + u < w && mr[u] >= 0;
-                const bool tr = (mr[u] & kMirT) != 0;
+                bool on, tr;
+                if constexpr (IX == kIxPack) {
+                    on = t0 + u < w && mr[u] != kIdxPad;
+                    tr = mr[u] != 0;  // another position: the transposed twin
+                } else {
+                    on = t0 + u < w && mr[u] >= 0;
+                    tr = (mr[u] & kMirT) != 0;
+                }
                 const V b1 = tr ? blk[u][2] : blk[u][1], b2 = tr ? blk[u][1] : blk[u][2];
                 a0 += on ? blk[u][0] * xj[u].x + b1 * xj[u].y : (V)0;
                 a1 += on ? b2 * xj[u].x + blk[u][3] * xj[u].y : (V)0;
@@ -316,9 +363,9 @@ __device__ __forceinline__ void spmv_row(const MatArgs<V> &mt, int32_t b, int32_
     // fp64 too: the fp64 A is bit-symmetric (the reference's mirrored
     // assignment, §2.2), so the transposed reads give the same bits
     if (mt.sell_mir)
-        spmv_row_t<true, V, ZH>(mt, b, i, x, y0, y1);
+        spmv_row_t<kIxMir, V, ZH>(mt, b, i, x, y0, y1);
     else
-        spmv_row_t<false, V, ZH>(mt, b, i, x, y0, y1);
+        spmv_row_t<kIxPlain, V, ZH>(mt, b, i, x, y0, y1);
 }
 
 // XCD-aware workgroup -> (row block, system): workgroups w and w+8 share an
@@ -400,6 +447,7 @@ struct MatH {
     int64_t sell_nb;
     const int32_t *sell_off, *sell_col;
     const int32_t *sell_mir;  // mirror table (symmetric reads), or null
+    const uint32_t *sell_idx; // packed index words (kIxPack; sell_index_pack), or null
     const int32_t *vptr;      // plain reads: row block counts (row_width), or null
     const uint2 *A;  // the level-0 sweep copy (h0_ld), [B][sell_nb] blocks
 };
@@ -409,11 +457,14 @@ struct MatH {
 // contraction, so every system slot rounds alike (a system's bits must not
 // depend on its slot, i.e. on the batch split). xload(t, j): system t's
 // operand of column j.
-template <bool sym, int NS, int U = kSweepU, typename XL>
+template <int IX, int NS, int U = kSweepU, typename XL>
 __device__ __forceinline__ void spmv_row_hx_ns(const MatH &mt, const int32_t (&bs)[NS], int32_t i, XL &&xload,
                                                float (&y)[NS][2], uint2 *diag = nullptr) {
 #pragma clang fp contract(off)
-    const int32_t s = i >> 6, l = i & 63;
+    constexpr bool sym = IX != kIxPlain;
+    // kIxPack: 32-bit positions, byte offsets from each system's base
+    using Pos = std::conditional_t<IX == kIxPack, uint32_t, int64_t>;
+    const int32_t s = wave_slice(i), l = i & 63;
     const int32_t o = mt.sell_off[s];
     const int32_t w = (mt.sell_off[s + 1] - o) >> 6;
     const int32_t wl = sym ? w : row_width(mt.vptr, i, w);  // this row's slots
@@ -421,24 +472,39 @@ __device__ __forceinline__ void spmv_row_hx_ns(const MatH &mt, const int32_t (&b
 #pragma unroll
     for (int t = 0; t < NS; ++t) acc[t][0] = acc[t][1] = 0.f;
     for (int32_t t0 = 0; t0 < w; t0 += U) {
-        int32_t j[U], mr[U];
-        int64_t pos[U];
+        int32_t j[U], mr[U];  // kIxPack: mr = the word's position delta
+        Pos pos[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            pos[u] = (int64_t)o + min(t0 + u, wl - 1) * kSlice + l;
-            j[u] = mt.sell_col[pos[u]];
-            if constexpr (sym) mr[u] = mt.sell_mir[pos[u]];
+            if constexpr (IX == kIxPack) {
+                const int32_t own = o + min(t0 + u, wl - 1) * kSlice + l;
+                const uint32_t iw = *byte_off(mt.sell_idx, (uint32_t)own * 4u);
+                j[u] = i + idx_dcol(iw);
+                mr[u] = idx_dpos(iw);
+                pos[u] = (uint32_t)(mr[u] == kIdxPad ? o + l : own + mr[u]);
+            } else {
+                pos[u] = (int64_t)o + min(t0 + u, wl - 1) * kSlice + l;
+                j[u] = mt.sell_col[pos[u]];
+                if constexpr (sym) mr[u] = mt.sell_mir[pos[u]];
+            }
         }
-        if constexpr (sym) {
+        if constexpr (IX == kIxMir) {
 #pragma unroll
             for (int u = 0; u < U; ++u) pos[u] = mir_pos(mr[u], (int64_t)o + l);
         }
         uint2 blk[NS][U];
         float2 xj[NS][U];
 #pragma unroll
-        for (int t = 0; t < NS; ++t)
+        for (int t = 0; t < NS; ++t) {
+            if constexpr (IX == kIxPack) {
+                const uint2 *Ab = mt.A + (int64_t)bs[t] * mt.sell_nb;
 #pragma unroll
-            for (int u = 0; u < U; ++u) blk[t][u] = h0_ld(mt.A, (int64_t)bs[t] * mt.sell_nb + pos[u]);
+                for (int u = 0; u < U; ++u) blk[t][u] = *byte_off(Ab, pos[u] * 8u);
+            } else {
+#pragma unroll
+                for (int u = 0; u < U; ++u) blk[t][u] = h0_ld(mt.A, (int64_t)bs[t] * mt.sell_nb + pos[u]);
+            }
+        }
         if (diag && t0 == 0) {  // slot 0: the diagonal block, never mirrored
 #pragma unroll
             for (int t = 0; t < NS; ++t) diag[t] = blk[t][0];
@@ -451,7 +517,10 @@ __device__ __forceinline__ void spmv_row_hx_ns(const MatH &mt, const int32_t (&b
         for (int u = 0; u < U; ++u) {
             bool on = t0 + u < wl;
             bool tr = false;
-            if constexpr (sym) {
+            if constexpr (IX == kIxPack) {
+                on = on && mr[u] != kIdxPad;
+                tr = mr[u] != 0;  // another position: the transposed twin
+            } else if constexpr (sym) {
                 on = on && mr[u] >= 0;
                 tr = (mr[u] & kMirT) != 0;
             }
@@ -506,7 +575,7 @@ __device__ __forceinline__ float2 bf16_diag_solve(uint2 a, float v0, float v1) {
 // slot 0 (the diagonal block) of row i of system b in a SELL-64 bf16 operator
 __device__ __forceinline__ uint2 bf16_diag_block(const uint2 *A, int64_t sell_nb, const int32_t *sell_off,
                                                  int32_t b, int32_t i) {
-    return h0_ld(A, (int64_t)b * sell_nb + sell_off[i >> 6] + (i & 63));
+    return h0_ld(A, (int64_t)b * sell_nb + sell_off[wave_slice(i)] + (i & 63));
 }
 
 }  // namespace

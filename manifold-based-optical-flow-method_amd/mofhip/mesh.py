@@ -293,3 +293,39 @@ class DeviceMesh:
             L.check(L.lib().mof_bench_spmv(self.handle(device), prec, int(batch), int(reps),
                                            ctypes.byref(ms), ctypes.byref(by)))
         return ms.value, by.value
+
+
+def index_probe(triangles, n_vertices: int, sym: int = -1, reorder: bool = True) -> dict:
+    """Host-only diagnostic (mof_index_probe): the level-0 SELL index tables
+    the library builds for this triangle list -- ``sell_off``, ``col``,
+    ``mir`` (position | 1 << 30 if transposed, -1 padding), the ``packed``
+    words, and whether symmetric reads (``sym_used``) and the packed words
+    (``packed_used``) are taken. ``sym``: 1 / 0 force symmetric / plain reads,
+    -1 decides per mesh, as ``MOF_SYM_READS`` does for a handle."""
+    T = np.ascontiguousarray(triangles, dtype=np.int32)
+    N, M = int(n_vertices), len(T)
+    flags = 0 if reorder else L.MOF_NO_REORDER
+    nb, su, pu = ctypes.c_int64(0), ctypes.c_int32(0), ctypes.c_int32(0)
+    L.check(L.lib().mof_index_probe(L.ptr(T), N, M, flags, int(sym), ctypes.byref(nb), None, None, None, None,
+                                    None, None))
+    off = np.zeros((N + 63) // 64 + 1, dtype=np.int32)
+    col = np.zeros(nb.value, dtype=np.int32)
+    mir = np.zeros(nb.value, dtype=np.int32)
+    packed = np.zeros(nb.value, dtype=np.uint32)
+    L.check(L.lib().mof_index_probe(L.ptr(T), N, M, flags, int(sym), ctypes.byref(nb), L.ptr(off), L.ptr(col),
+                                    L.ptr(mir), L.ptr(packed), ctypes.byref(su), ctypes.byref(pu)))
+    return {"sell_off": off, "col": col, "mir": mir, "packed": packed, "sym_used": bool(su.value),
+            "packed_used": bool(pu.value)}
+
+
+class force_index32:
+    """Tests only (mof_test_force_index32): handles created inside the block
+    keep the two 32-bit index tables where the packed words would fit."""
+
+    def __enter__(self):
+        L.check(L.lib().mof_test_force_index32(1))
+        return self
+
+    def __exit__(self, *exc):
+        L.check(L.lib().mof_test_force_index32(0))
+        return False
