@@ -259,6 +259,32 @@ int mof_velocity_vectors(int32_t device, const double *e, const double *V, int32
                          int32_t K, double *V_coord, double *speed, uint32_t flags,
                          void *stream);
 
+/* the wave speed of S5_compute_wave_v.py on a mesh handle,
+ * speed = (dX/dt) / |grad_M X| per vertex and frame, signed (the script's
+ * / 1000 and abs, S5:312-313, stay with the caller). X (T, N) f64 in the
+ * caller's vertex order holds phases (MOF_WAVE_PHASE: wave_velocity_phase,
+ * S5:79-123, with the wrapped differences of compute_temporal_gradient_phase
+ * and angle_subtract, S5:60-77, 225-233; T >= 2) or amplitudes
+ * (wave_velocity_amplitude, S5:14-58: np.gradient(X, axis=0, edge_order=2) /
+ * dt, S5:24; T >= 3). Outputs, any of them NULL but not all: speed (T, N);
+ * grad_norm (T, N), the length of the tangent components; dXdt (T, N),
+ * bit-identical to numpy; grad_ab (T, N, 2), the components (alpha, beta) of
+ * the vertex gradient on e_i (compute_grad_M_I, project_vector_to_plane,
+ * express_vector_on_basis, S5:136-191; the triangles of a vertex in ascending
+ * index). speed is the IEEE quotient dXdt / grad_norm: +-inf or NaN where the
+ * gradient vanishes, as numpy's division gives. The spatial steps are applied
+ * as one sparse operator on the vertex adjacency (built on the handle at the
+ * first call, from its e, grad_w and areas), equal to the reference's loops to
+ * rounding: |grad_ab - ref| <= 1e-13 max|grad_M|. Host pointers, or device
+ * pointers on the handle's device with MOF_IO_DEVICE (stream: hipStream_t or
+ * NULL). frames_per_pass: frames handled per pass over X (0: chosen so that
+ * the device workspace stays bounded whatever T is); the results do not
+ * depend on it. */
+#define MOF_WAVE_PHASE 512u     /* mof_wave_speed: X holds phases */
+int mof_wave_speed(mof_mesh *mesh, const double *X, int32_t T, double dt, uint32_t flags,
+                   int32_t frames_per_pass, void *stream, double *speed, double *grad_norm,
+                   double *dXdt, double *grad_ab);
+
 /* find_singularity_points(coordinates, triangles, V_now,
  * eps) (find_singularity_point.py:140-189) for K velocity fields V_coord
  * (K,N,3) at once. coords (N,3) f64, or f32 with MOF_COORDS_F32 (pyvista

@@ -741,6 +741,8 @@ int mof_mesh_destroy(mof_mesh *m) {
                 if (e) (void)hipEventDestroy(e);
             mof::amg_destroy(m->amg);
             m->amg = nullptr;
+            mof::wave_destroy(m->wave);
+            m->wave = nullptr;
             if (m->stream) (void)hipStreamDestroy(m->stream);
             m->stream = nullptr;
             delete m;  // DevArray destructors free on the current (guarded) device
@@ -993,6 +995,27 @@ int mof_velocity_vectors(int32_t device, const double *e, const double *V, int32
             MOF_HIP(hipMemcpyAsync(V_coord, dc.p, 3 * nk * sizeof(double), hipMemcpyDeviceToHost, s));
         if (speed) MOF_HIP(hipMemcpyAsync(speed, dsp.p, nk * sizeof(double), hipMemcpyDeviceToHost, s));
         MOF_HIP(hipStreamSynchronize(s));
+    });
+}
+
+int mof_wave_speed(mof_mesh *m, const double *X, int32_t T, double dt, uint32_t flags, int32_t frames_per_pass,
+                   void *stream, double *speed, double *grad_norm, double *dXdt, double *grad_ab) {
+    return guarded([&] {
+        MOF_REQUIRE(m, "mesh is NULL");
+        MOF_REQUIRE(X, "X is NULL");
+        const bool phase = (flags & MOF_WAVE_PHASE) != 0;
+        MOF_REQUIRE(T >= (phase ? 2 : 3), phase ? "phase mode needs T >= 2 frames (S5:60-77)"
+                                                : "amplitude mode needs T >= 3 frames (np.gradient, edge_order=2)");
+        MOF_REQUIRE(dt != 0.0, "dt is 0");
+        MOF_REQUIRE(frames_per_pass >= 0, "frames_per_pass is negative");
+        MOF_REQUIRE(speed || grad_norm || dXdt || grad_ab, "every output is NULL");
+        mof::mesh_join_prep(m);
+        DeviceGuard dg(m->device);
+        const bool dev_io = (flags & MOF_IO_DEVICE) != 0;
+        hipStream_t s = stream ? (hipStream_t)stream : m->stream;
+        int32_t fpp = frames_per_pass > 0 ? frames_per_pass : mof::wave_auto_frames(m->N, T);
+        fpp = std::min(fpp, 1 << 16);  // the gather's grid: one y index per group of frames
+        mof::wave_speed(m, X, T, dt, phase, fpp, dev_io, s, speed, grad_norm, dXdt, grad_ab);
     });
 }
 

@@ -200,6 +200,7 @@ constexpr int kSysStride = 12;
 struct AmgDevice;     // mof_amg.h
 struct AmgHierarchy;  // mof_amg.h
 class HostStage;      // mof_hostio.h
+struct WaveState;     // mof_wave.hip
 
 // Host state of one mesh shared by its handles on several devices
 // (mof_mesh_create builds it once, mof_mesh_clone reuses it): the inputs in
@@ -301,6 +302,9 @@ struct mof_mesh {
     // host state shared with the clones of this mesh on other devices
     std::shared_ptr<mof::MeshShared> shared;
     hipEvent_t hev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // mof_wave_speed: the gradient operator's coefficient table and the pass
+    // workspace, built on first use (mof_wave.hip)
+    mof::WaveState *wave = nullptr;
 };
 
 namespace mof {
@@ -331,6 +335,15 @@ void launch_singularities_compact(int32_t N, int32_t M, int32_t K, const void *c
                                   hipStream_t s);
 void launch_velocity_vectors(int32_t N, int32_t K, const double *e, const double *V, double *Vc,
                              double *speed, hipStream_t s);
+
+// mof_wave_speed (mof_wave.hip): X (T, N) and the outputs (any may be null)
+// in the caller's vertex order, device pointers (dev_io) or host pointers
+// staged pass by pass; fpp > 0 frames per pass. Synchronises s.
+void wave_speed(mof_mesh *m, const double *X, int32_t T, double dt, bool phase, int32_t fpp, bool dev_io,
+                hipStream_t s, double *speed, double *gnorm, double *dxdt, double *gab);
+// frames per pass the library chooses for N vertices: bounds the pass workspace whatever T is
+int32_t wave_auto_frames(int32_t N, int32_t T);
+void wave_destroy(WaveState *w);
 
 // Timed SpMV launches: each is charged with the systems it actually
 // processed (a system that converged, or failed, earlier in a chunk of

@@ -11,3 +11,5 @@ from ._lib import (MofError, NotConverged, build_native, device_count, lib,  # n
 from .mesh import DeviceMesh  # noqa: F401
 from .decomp import DecomposedMesh, partition_rcb, plan_info  # noqa: F401
 from .solve import velocity_field_sharded, shard_ranges  # noqa: F401
+from .wave import (wave_speed, wave_velocity_phase, wave_velocity_amplitude,  # noqa: F401
+                   compute_temporal_gradient_phase)

@@ -42,6 +42,7 @@ MOF_SOLVE_EAGER = 256
 MOF_CSV_ROUND_TRIP = 1
 MOF_COORDS_F32 = 32
 MOF_DD_STAGED = 64
+MOF_WAVE_PHASE = 512
 MOF_CSR_A2 = 0
 MOF_CSR_A_LAST = 1
 
@@ -56,7 +57,7 @@ EXPORTS = (
     "mof_dd_create_rank", "mof_dd_destroy", "mof_dd_get_info", "mof_dd_solve_range",
     "mof_dd_test_fail_recovery_alloc", "mof_mesh_prepare", "mof_mesh_sync",
     "mof_singularities_compact", "mof_xcd_map_check", "mof_xcd_batch_cap", "mof_dd_create_rank_host",
-    "mof_index_probe", "mof_test_force_index32",
+    "mof_index_probe", "mof_test_force_index32", "mof_wave_speed",
 )
 
 
@@ -181,6 +182,7 @@ def lib():
             "mof_ply_read": ([ctypes.c_char_p, P, P, P], ctypes.c_int),
             "mof_point_normals": ([P, P, i64, i64, P], ctypes.c_int),
             "mof_cell_areas": ([P, P, i64, i64, P], ctypes.c_int),
+            "mof_wave_speed": ([P, P, i32, f64, u32, i32, P, P, P, P, P], ctypes.c_int),
             "mof_singularities": ([i32, P, P, i32, i32, P, i32, f64, u32, P, P, P, P, P],
                                   ctypes.c_int),
             "mof_amg_probe": ([P, P, i32, i32, P, P, P, P], ctypes.c_int),
