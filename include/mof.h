@@ -285,6 +285,45 @@ int mof_wave_speed(mof_mesh *mesh, const double *X, int32_t T, double dt, uint32
                    int32_t frames_per_pass, void *stream, double *speed, double *grad_norm,
                    double *dXdt, double *grad_ab);
 
+/* the streamlines of S6_streamline.py on a mesh handle, for
+ * K fields V_coord (K, N, 3) f64 in the caller's vertex order. The
+ * reference's greedy walk (S6:51-138) chooses the next vertex from (field,
+ * vertex) alone, so its result is a successor map plus a walk along it:
+ *   next (K, N): the neighbour j of vertex i with the largest
+ *     d_j = u_j . V_i, u_j the normalised projection of p_j - p_i on the
+ *     tangent plane of e_i (S6:63-77; on a MOF_GEOM_F32_POINTS handle the
+ *     difference is formed in float32), the smallest vertex id on equal
+ *     maxima; -1 (terminal) unless d_j > 0 -- a zero or NaN V_i is terminal --
+ *     or where the boundary-edge test of S6:100-133 fails (i in fewer than 6
+ *     triangles and sharing exactly one with j; restated as written);
+ *   length (K, N): the vertices of the walk s, next[s], next[next[s]], ...
+ *     from seed s, which ends before the first vertex that is terminal-exited
+ *     or already on the path (vertices compared by id); 0 where the seed is
+ *     skipped because V_s . V_s == 0 (S6:29).
+ * Either output may be NULL, not both. Host pointers, or device pointers on
+ * the handle's device with MOF_IO_DEVICE (stream: hipStream_t or NULL). The
+ * fields go through in passes, so the device workspace stays bounded whatever
+ * K is; the per-slot directions u_j are built on the handle at the first call. */
+int mof_streamline_map(mof_mesh *mesh, const double *V_coord, int32_t K, uint32_t flags, void *stream,
+                       int32_t *next, int32_t *length);
+
+/* The same as the reference's list-shaped result
+ * (track_static_vectorfields_over_time, S6:17-37): the walks with
+ * length >= min_length (and > 0), field-major, seeds ascending within a
+ * field, compacted on the device. n_lines (K, may be NULL): lines per field;
+ * line_off: totals[0] + 1 offsets into line_vtx; line_vtx: the vertex ids of
+ * the lines, totals[1] in all. cap_lines / cap_vertices: the capacities of
+ * line_off (less one) and line_vtx. totals[0..1] always receives the line and
+ * vertex counts, and MOF_E_ARG is returned when either exceeds its cap (call
+ * again, sized; a list may be NULL when its cap is 0). Lists are host
+ * outputs; V_coord host, or device with MOF_IO_DEVICE. */
+int mof_streamlines(mof_mesh *mesh, const double *V_coord, int32_t K, int32_t min_length, uint32_t flags,
+                    void *stream, int64_t cap_lines, int64_t cap_vertices, int64_t *totals, int64_t *n_lines,
+                    int64_t *line_off, int32_t *line_vtx);
+/* Tests only: the two calls above take `fields` fields per pass (0: the
+ * library's choice). The results do not depend on it. */
+int mof_test_streamline_pass(int32_t fields);
+
 /* find_singularity_points(coordinates, triangles, V_now,
  * eps) (find_singularity_point.py:140-189) for K velocity fields V_coord
  * (K,N,3) at once. coords (N,3) f64, or f32 with MOF_COORDS_F32 (pyvista

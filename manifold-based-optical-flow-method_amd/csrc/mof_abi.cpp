@@ -743,6 +743,8 @@ int mof_mesh_destroy(mof_mesh *m) {
             m->amg = nullptr;
             mof::wave_destroy(m->wave);
             m->wave = nullptr;
+            mof::stream_destroy(m->sline);
+            m->sline = nullptr;
             if (m->stream) (void)hipStreamDestroy(m->stream);
             m->stream = nullptr;
             delete m;  // DevArray destructors free on the current (guarded) device
@@ -1017,6 +1019,45 @@ int mof_wave_speed(mof_mesh *m, const double *X, int32_t T, double dt, uint32_t 
         fpp = std::min(fpp, 1 << 16);  // the gather's grid: one y index per group of frames
         mof::wave_speed(m, X, T, dt, phase, fpp, dev_io, s, speed, grad_norm, dXdt, grad_ab);
     });
+}
+
+int mof_streamline_map(mof_mesh *m, const double *V_coord, int32_t K, uint32_t flags, void *stream, int32_t *next,
+                       int32_t *length) {
+    return guarded([&] {
+        MOF_REQUIRE(m, "mesh is NULL");
+        MOF_REQUIRE(V_coord, "V_coord is NULL");
+        MOF_REQUIRE(K >= 1, "K < 1 fields");
+        MOF_REQUIRE(next || length, "every output is NULL");
+        mof::mesh_join_prep(m);
+        DeviceGuard dg(m->device);
+        hipStream_t s = stream ? (hipStream_t)stream : m->stream;
+        mof::stream_map(m, V_coord, K, (flags & MOF_IO_DEVICE) != 0, s, next, length);
+    });
+}
+
+int mof_streamlines(mof_mesh *m, const double *V_coord, int32_t K, int32_t min_length, uint32_t flags, void *stream,
+                    int64_t cap_lines, int64_t cap_vertices, int64_t *totals, int64_t *n_lines, int64_t *line_off,
+                    int32_t *line_vtx) {
+    return guarded([&] {
+        MOF_REQUIRE(m, "mesh is NULL");
+        MOF_REQUIRE(V_coord, "V_coord is NULL");
+        MOF_REQUIRE(K >= 1, "K < 1 fields");
+        MOF_REQUIRE(cap_lines >= 0 && cap_vertices >= 0, "negative list capacity");
+        MOF_REQUIRE(totals, "every output is NULL (totals)");
+        MOF_REQUIRE((line_off || cap_lines == 0) && (line_vtx || cap_vertices == 0), "NULL list with a capacity");
+        mof::mesh_join_prep(m);
+        DeviceGuard dg(m->device);
+        hipStream_t s = stream ? (hipStream_t)stream : m->stream;
+        const bool fits = mof::stream_lists(m, V_coord, K, min_length, (flags & MOF_IO_DEVICE) != 0, s, cap_lines,
+                                            cap_vertices, totals, n_lines, line_off, line_vtx);
+        MOF_REQUIRE(fits, "streamline lists exceed cap_lines / cap_vertices: " + std::to_string(totals[0]) +
+                              " lines, " + std::to_string(totals[1]) + " vertices (totals)");
+    });
+}
+
+int mof_test_streamline_pass(int32_t fields) {
+    mof::g_stream_pass_fields.store(fields > 0 ? fields : 0);
+    return MOF_OK;
 }
 
 int mof_singularities(int32_t device, const void *coords, const int32_t *triangles, int32_t N, int32_t M,

@@ -201,6 +201,7 @@ struct AmgDevice;     // mof_amg.h
 struct AmgHierarchy;  // mof_amg.h
 class HostStage;      // mof_hostio.h
 struct WaveState;     // mof_wave.hip
+struct StreamState;   // mof_streamline.hip
 
 // Host state of one mesh shared by its handles on several devices
 // (mof_mesh_create builds it once, mof_mesh_clone reuses it): the inputs in
@@ -305,6 +306,9 @@ struct mof_mesh {
     // mof_wave_speed: the gradient operator's coefficient table and the pass
     // workspace, built on first use (mof_wave.hip)
     mof::WaveState *wave = nullptr;
+    // mof_streamline_map / mof_streamlines: the per-slot direction table and
+    // the pass workspace, built on first use (mof_streamline.hip)
+    mof::StreamState *sline = nullptr;
 };
 
 namespace mof {
@@ -344,6 +348,19 @@ void wave_speed(mof_mesh *m, const double *X, int32_t T, double dt, bool phase, 
 // frames per pass the library chooses for N vertices: bounds the pass workspace whatever T is
 int32_t wave_auto_frames(int32_t N, int32_t T);
 void wave_destroy(WaveState *w);
+
+// mof_streamline_map (mof_streamline.hip): V (K, N, 3) and next / length
+// (K, N; either may be null) in the caller's vertex order, device pointers
+// (dev_io) or host pointers staged pass by pass. Synchronises s.
+void stream_map(mof_mesh *m, const double *V, int32_t K, bool dev_io, hipStream_t s, int32_t *next, int32_t *length);
+// mof_streamlines: the kept lines as lists (host outputs), compacted on the
+// device pass by pass; totals always written; false when a cap is exceeded
+bool stream_lists(mof_mesh *m, const double *V, int32_t K, int32_t min_len, bool dev_io, hipStream_t s,
+                  int64_t cap_lines, int64_t cap_vertices, int64_t *totals, int64_t *n_lines, int64_t *line_off,
+                  int32_t *line_vtx);
+void stream_destroy(StreamState *st);
+// tests only (mof_test_streamline_pass): fields per pass of the two calls above, 0 = the library's choice
+extern std::atomic<int> g_stream_pass_fields;
 
 // Timed SpMV launches: each is charged with the systems it actually
 // processed (a system that converged, or failed, earlier in a chunk of

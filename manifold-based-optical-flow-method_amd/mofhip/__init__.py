@@ -13,3 +13,5 @@ from .decomp import DecomposedMesh, partition_rcb, plan_info  # noqa: F401
 from .solve import velocity_field_sharded, shard_ranges  # noqa: F401
 from .wave import (wave_speed, wave_velocity_phase, wave_velocity_amplitude,  # noqa: F401
                    compute_temporal_gradient_phase)
+from .streamline import (streamline_map, streamline_map_device, streamline_lists,  # noqa: F401
+                         track_static_vectorfields_over_time, extract_static_streamline_dot_product)

@@ -57,7 +57,8 @@ EXPORTS = (
     "mof_dd_create_rank", "mof_dd_destroy", "mof_dd_get_info", "mof_dd_solve_range",
     "mof_dd_test_fail_recovery_alloc", "mof_mesh_prepare", "mof_mesh_sync",
     "mof_singularities_compact", "mof_xcd_map_check", "mof_xcd_batch_cap", "mof_dd_create_rank_host",
-    "mof_index_probe", "mof_test_force_index32", "mof_wave_speed",
+    "mof_index_probe", "mof_test_force_index32", "mof_wave_speed", "mof_streamline_map", "mof_streamlines",
+    "mof_test_streamline_pass",
 )
 
 
@@ -183,6 +184,9 @@ def lib():
             "mof_point_normals": ([P, P, i64, i64, P], ctypes.c_int),
             "mof_cell_areas": ([P, P, i64, i64, P], ctypes.c_int),
             "mof_wave_speed": ([P, P, i32, f64, u32, i32, P, P, P, P, P], ctypes.c_int),
+            "mof_streamline_map": ([P, P, i32, u32, P, P, P], ctypes.c_int),
+            "mof_streamlines": ([P, P, i32, i32, u32, P, i64, i64, P, P, P, P], ctypes.c_int),
+            "mof_test_streamline_pass": ([i32], ctypes.c_int),
             "mof_singularities": ([i32, P, P, i32, i32, P, i32, f64, u32, P, P, P, P, P],
                                   ctypes.c_int),
             "mof_amg_probe": ([P, P, i32, i32, P, P, P, P], ctypes.c_int),
