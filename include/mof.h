@@ -423,6 +423,32 @@ int mof_index_probe(const int32_t *tri, int32_t N, int32_t M, uint32_t flags, in
  * path's results are compared with it bit for bit. */
 int mof_test_force_index32(int32_t on);
 
+/* Diagnostic (host only): the staged fp64 residual of the mixed-precision
+ * refinement keeps, per 64-row slice of the internal vertex order, the mesh
+ * geometry every system shares in LDS: 64 x (36 B per a2 slot + 192 B per
+ * incidence slot + 48 B). *staged_bytes: the largest slice of the mesh given
+ * by tri (M x 3) over N vertices, laid out as mof_mesh_create lays it out
+ * (flags: MOF_NO_REORDER); *staged_used (may be NULL): it fits the kernel's
+ * fixed 160 KiB limit, so a handle of the mesh takes the staged kernel --
+ * otherwise (wide irregular meshes) the row kernel. The batch plays no part. */
+int mof_residual_probe(const int32_t *tri, int32_t N, int32_t M, uint32_t flags, int64_t *staged_bytes,
+                       int32_t *staged_used);
+/* Test hook (never read from the environment): every mesh and decomposed part
+ * created after mof_test_force_residual_rows(1) keeps the row kernel of the
+ * fp64 residual even where the staged one fits (0: back to the default) --
+ * the staged kernel's results are compared with it bit for bit. */
+int mof_test_force_residual_rows(int32_t on);
+/* Test hook: small launches of the staged residual run one system pair per
+ * wave, large ones (the flagship's) four in turn; after
+ * mof_test_force_residual_trips(1) every staged launch takes the four-trip
+ * kernel, so small meshes exercise it (0: back to the default). */
+int mof_test_force_residual_trips(int32_t on);
+/* Test hook: counts[0..2] = launches so far in this process of the fp64
+ * residual's row kernel, of the staged kernel with one trip per wave and of
+ * the staged kernel with four -- what a handle (or a decomposed part)
+ * really ran, whatever the probe says. */
+int mof_test_residual_launches(int64_t *counts);
+
 /* Diagnostic (host only): checks that the XCD-aware workgroup order of the
  * row kernels -- nblk row blocks x batch systems, walked in groups of
  * `group` systems (0: all) -- visits every (row block, system) pair exactly

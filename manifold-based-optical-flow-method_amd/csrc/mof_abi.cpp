@@ -447,6 +447,9 @@ int mof_io_guard(const std::function<void()> &f) { return guarded(f); }
 namespace mof {
 
 std::atomic<int> g_force_index32{0};
+std::atomic<int> g_force_residual_rows{0};
+std::atomic<int> g_force_residual_trips{0};
+std::atomic<int64_t> g_residual_launches[3];
 
 void mesh_set_own(mof_mesh *m, int32_t nown) {
     MOF_HIP(hipSetDevice(m->device));
@@ -481,6 +484,8 @@ void mesh_set_own(mof_mesh *m, int32_t nown) {
         m->sell_idx.alloc(mt->packed.size());
         m->sell_idx.upload(mt->packed.data(), mt->packed.size(), m->stream);
     }
+    m->res_lds_bytes = res_staged_bytes(m->pat);
+    m->res_lds = m->res_lds_bytes <= kResLdsCap && !g_force_residual_rows.load();
     int64_t own = 0;  // positions read at their own place: diagonal + upper blocks
     for (int32_t v : mir) own += v >= 0 && !(v & kMirT);
     m->blocks_read = own;
@@ -1262,6 +1267,33 @@ int mof_index_probe(const int32_t *tri, int32_t N, int32_t M, uint32_t flags, in
 
 int mof_test_force_index32(int32_t on) {
     return guarded([&] { mof::g_force_index32.store(on != 0); });
+}
+
+int mof_residual_probe(const int32_t *tri, int32_t N, int32_t M, uint32_t flags, int64_t *staged_bytes,
+                       int32_t *staged_used) {
+    return guarded([&] {
+        MOF_REQUIRE(tri && staged_bytes && N > 0 && M > 0, "bad arguments");
+        mof_mesh m;  // the internal order and pattern of mof_mesh_create (host half only)
+        const std::vector<double> zero(3 * (size_t)std::max(N, M), 0.0);
+        mof::mesh_prepare_host(&m, zero.data(), zero.data(), tri, zero.data(), N, M, flags, nullptr, nullptr);
+        *staged_bytes = mof::res_staged_bytes(m.pat);
+        if (staged_used) *staged_used = *staged_bytes <= mof::kResLdsCap;
+    });
+}
+
+int mof_test_force_residual_rows(int32_t on) {
+    return guarded([&] { mof::g_force_residual_rows.store(on != 0); });
+}
+
+int mof_test_force_residual_trips(int32_t on) {
+    return guarded([&] { mof::g_force_residual_trips.store(on != 0); });
+}
+
+int mof_test_residual_launches(int64_t *counts) {
+    return guarded([&] {
+        MOF_REQUIRE(counts, "NULL argument");
+        for (int k = 0; k < 3; ++k) counts[k] = mof::g_residual_launches[k].load();
+    });
 }
 
 int mof_xcd_map_check(int32_t nblk, int32_t batch, int32_t group) {

@@ -143,6 +143,25 @@ std::vector<int32_t> sell_mirror(const Pattern &pat, int32_t nown, int sym, bool
 std::vector<uint32_t> sell_index_pack(const Pattern &pat, const std::vector<int32_t> &mir);
 // tests only (mof_test_force_index32): every mesh set up from now on keeps the 32-bit tables
 extern std::atomic<int> g_force_index32;
+// The staged fp64 residual (k_residual_lds, mof_pcg.hip) keeps the geometry
+// all systems share of one 64-row slice in LDS: per row 36 B per a2 slot
+// (column + fp64 block), 192 B per incidence slot (tinc record, 9 hat
+// gradients, two vertices' tangent bases, A_T / 12) and 48 B (its own bases).
+// A mesh (or decomposed part) takes the kernel when its widest slice fits
+// kResLdsCap, the fixed dynamic-LDS limit the kernel is given; the decision
+// depends on the pattern alone, never on the batch.
+constexpr int64_t kResLdsCap = 160 * 1024;
+inline int64_t res_slice_bytes(int32_t w_a2, int32_t w_inc) {
+    return (int64_t)kSlice * ((int64_t)w_a2 * 36 + (int64_t)w_inc * 192 + 48);
+}
+int64_t res_staged_bytes(const Pattern &pat);  // the maximum over the slices
+// tests only (mof_test_force_residual_rows): every mesh set up from now on keeps k_residual_rcn
+extern std::atomic<int> g_force_residual_rows;
+// tests only (mof_test_force_residual_trips): the staged kernel's multi-trip instance whatever the
+// launch's size (launch_residual_lds otherwise gives small launches one pair per wave)
+extern std::atomic<int> g_force_residual_trips;
+// launches so far of k_residual_rcn, the one-trip and the multi-trip k_residual_lds (mof_test_residual_launches)
+extern std::atomic<int64_t> g_residual_launches[3];
 
 // Per-batch device workspace (capacity B systems).
 struct Workspace {
@@ -160,6 +179,7 @@ struct Workspace {
     DevArray<double> part_pq;          // [B][nblk]
     DevArray<double> part_rzrr;        // [2][B][nblk][2]
     DevArray<double> part_rr0;         // [B][nblk][2]
+    DevArray<double> res_spart;        // [B][nslices][2] per-slice |r|^2, |f|^2 (k_residual_lds), if used
     DevArray<double> part_dx;          // [B][nvb][2]: max|d|, max|x64| per k_outer_update block
     DevArray<double> sc;               // pre-reduced PCG scalars: r.z, |r|^2 [2][B][2], p.q [2][B]
     DevArray<double> sysd;             // [B][8] per-system scalars
@@ -273,6 +293,9 @@ struct mof_mesh {
     // kernels keep the 32-bit tables
     mof::DevArray<uint32_t> sell_idx;
     bool idx_packed = false;
+    // the re-forming fp64 residual runs staged in LDS (res_staged_bytes <= kResLdsCap)
+    int64_t res_lds_bytes = 0;
+    bool res_lds = false;
     mof::DevArray<double> e, gw, iw, area, a2;  // a2: [sell_nb][4] (unscaled, bit-exact)
     // operator copies: lambda*a2 (cached per lambda) and A_T/12 with a zero slot M
     mof::DevArray<double> a2s64, w12_64;

@@ -242,6 +242,12 @@ __device__ __forceinline__ double dot3_np(const double *x, const double *y) {
 // them (the residual is bound by those shared gathers). No fp contraction, so
 // every system slot rounds alike (a system's bits must not depend on the slot
 // it lands in, i.e. on the batch split).
+// One a2 slot's term of one system (shared by the row and the staged kernel).
+__device__ __forceinline__ void rcn_a2_term(const double (&blk)[4], double2 xj, bool on, double (&acc)[2]) {
+#pragma clang fp contract(off)
+    acc[0] += on ? blk[0] * xj.x + blk[1] * xj.y : 0.0;
+    acc[1] += on ? blk[2] * xj.x + blk[3] * xj.y : 0.0;
+}
 // rcn_a2: acc += (lambda a2 x)_i, slots in order, kResU per load batch.
 template <int NS>
 __device__ __forceinline__ void rcn_a2(const OpArgs<double> &op, const int32_t (&bs)[NS], int32_t i,
@@ -261,11 +267,8 @@ __device__ __forceinline__ void rcn_a2(const OpArgs<double> &op, const int32_t (
         for (int u = 0; u < kResU; ++u) {
             const bool on = t0 + u < w;
 #pragma unroll
-            for (int t = 0; t < NS; ++t) {
-                const double2 xj = ld2(x64 + 2 * ((int64_t)bs[t] * op.N + j[u]));
-                acc[t][0] += on ? blk[u][0] * xj.x + blk[u][1] * xj.y : 0.0;
-                acc[t][1] += on ? blk[u][2] * xj.x + blk[u][3] * xj.y : 0.0;
-            }
+            for (int t = 0; t < NS; ++t)
+                rcn_a2_term(blk[u], ld2(x64 + 2 * ((int64_t)bs[t] * op.N + j[u])), on, acc[t]);
         }
     }
 }
@@ -286,6 +289,31 @@ __device__ __forceinline__ void rcn_row(const OpArgs<double> &op, const int32_t 
     }
 #pragma unroll
     for (int q = 0; q < 6; ++q) R.ei[q] = op.e[6 * (int64_t)i + q];
+}
+// One incidence's term of one system from its operands (shared by the row
+// and the staged kernel): corner c of the triangle, its hat gradients g, the
+// tangent bases of the row and of the corner's two other vertices, A_T / 12,
+// and the system's I values and x at the three vertices.
+__device__ __forceinline__ void rcn_tri_term(int c, const double (&g)[9], const double (&ei)[6],
+                                             const double (&ej)[6], const double (&ek)[6], double wt, double Ii,
+                                             double Ij, double Ik, double2 xi, double2 xj, double2 xk,
+                                             double (&val)[2]) {
+#pragma clang fp contract(off)
+    const double c0 = c == 0 ? Ii : (c == 1 ? Ik : Ij);
+    const double c1 = c == 0 ? Ij : (c == 1 ? Ii : Ik);
+    const double c2 = c == 0 ? Ik : (c == 1 ? Ij : Ii);
+    double gI[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) gI[d] = (c0 * g[d] + c1 * g[3 + d]) + c2 * g[6 + d];
+    const double2 ui = make_double2(dot3_np(gI, ei), dot3_np(gI, ei + 3));
+    const double2 uj = make_double2(dot3_np(gI, ej), dot3_np(gI, ej + 3));
+    const double2 uk = make_double2(dot3_np(gI, ek), dot3_np(gI, ek + 3));
+    const double si = ui.x * xi.x + ui.y * xi.y;
+    const double sj = uj.x * xj.x + uj.y * xj.y;
+    const double sk = uk.x * xk.x + uk.y * xk.y;
+    const double cc = wt * ((si + si) + sj + sk);
+    val[0] = ui.x * cc;
+    val[1] = ui.y * cc;
 }
 // rcn_tri: the term of incidence q (triangle, corner, the corner's two other
 // vertices) of row i, (a1_T x)_i = u_{T,i} (A_T/12) (2 s_i + s_j + s_k) with
@@ -317,25 +345,8 @@ __device__ __forceinline__ void rcn_tri(const OpArgs<double> &op, const int32_t 
         xk[t] = ld2(x64 + 2 * (vb + q.w));
     }
     wt = op.w12[q.x];
-    const int c = q.y;
 #pragma unroll
-    for (int t = 0; t < NS; ++t) {
-        const double c0 = c == 0 ? R.Ii[t] : (c == 1 ? Ik[t] : Ij[t]);
-        const double c1 = c == 0 ? Ij[t] : (c == 1 ? R.Ii[t] : Ik[t]);
-        const double c2 = c == 0 ? Ik[t] : (c == 1 ? Ij[t] : R.Ii[t]);
-        double gI[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) gI[d] = (c0 * g[d] + c1 * g[3 + d]) + c2 * g[6 + d];
-        const double2 ui = make_double2(dot3_np(gI, R.ei), dot3_np(gI, R.ei + 3));
-        const double2 uj = make_double2(dot3_np(gI, ej), dot3_np(gI, ej + 3));
-        const double2 uk = make_double2(dot3_np(gI, ek), dot3_np(gI, ek + 3));
-        const double si = ui.x * R.xi[t].x + ui.y * R.xi[t].y;
-        const double sj = uj.x * xj[t].x + uj.y * xj[t].y;
-        const double sk = uk.x * xk[t].x + uk.y * xk[t].y;
-        const double cc = wt * ((si + si) + sj + sk);
-        val[t][0] = ui.x * cc;
-        val[t][1] = ui.y * cc;
-    }
+    for (int t = 0; t < NS; ++t) rcn_tri_term(q.y, g, R.ei, ej, ek, wt, R.Ii[t], Ij[t], Ik[t], R.xi[t], xj[t], xk[t], val[t]);
 }
 
 // (A x)_i of NS systems: the a2 slots, then the incident triangles in
@@ -957,6 +968,19 @@ __global__ __launch_bounds__(kWG) void k_residual(OpArgs<double> op, int32_t nbl
 // staged in LDS and added by the row's thread in slot order (bit-identical):
 // 8421 / 5539 vs 5093 us per launch.
 constexpr int kResNS = 2;
+// Row vi's r = f - y of one system, stored when the system is active, and its
+// share of |r|^2, |f|^2 (owned rows only); shared by the row and the staged kernel.
+__device__ __forceinline__ void rcn_out(int64_t vi, bool own, bool act, const double (&y)[2],
+                                        const double *__restrict__ rhs, double *__restrict__ r64, double &rr,
+                                        double &ff) {
+    const double2 f = *reinterpret_cast<const double2 *>(rhs + 2 * vi);
+    const double r0 = f.x - y[0], r1 = f.y - y[1];
+    if (act) *reinterpret_cast<double2 *>(r64 + 2 * vi) = make_double2(r0, r1);
+    if (own) {
+        rr += r0 * r0 + r1 * r1;
+        ff += f.x * f.x + f.y * f.y;
+    }
+}
 template <int NS>
 __global__ __launch_bounds__(kWG) void k_residual_rcn(OpArgs<double> op, int32_t nblk, int32_t B, RedArgs rd,
                                                       const double *__restrict__ rhs,
@@ -988,14 +1012,7 @@ __global__ __launch_bounds__(kWG) void k_residual_rcn(OpArgs<double> op, int32_t
         apply_row_rcn<NS>(op, bs, i, x64, y);
 #pragma unroll
         for (int t = 0; t < NS; ++t) {
-            const int64_t vi = (int64_t)bs[t] * N + i;
-            const double2 f = *reinterpret_cast<const double2 *>(rhs + 2 * vi);
-            const double r0 = f.x - y[t][0], r1 = f.y - y[t][1];
-            if (act[t]) *reinterpret_cast<double2 *>(r64 + 2 * vi) = make_double2(r0, r1);
-            if (i < rd.nown) {
-                v[2 * t] += r0 * r0 + r1 * r1;
-                v[2 * t + 1] += f.x * f.x + f.y * f.y;
-            }
+            rcn_out((int64_t)bs[t] * N + i, i < rd.nown, act[t], y[t], rhs, r64, v[2 * t], v[2 * t + 1]);
         }
     }
     block_sum<2 * NS>(v, lds);
@@ -1008,6 +1025,221 @@ __global__ __launch_bounds__(kWG) void k_residual_rcn(OpArgs<double> op, int32_t
             o[1] = v[2 * t + 1];
         }
     }
+}
+
+// The re-forming residual with a row slice's geometry staged in LDS: a
+// workgroup is one SELL-64 slice x W waves, lane l of every wave is row
+// 64 s + l, and wave w takes the system pairs chunk (W TRIPS) + trip W + w.
+// What apply_row_rcn gathers per system pair and that is the same for every
+// system -- the slice's a2 columns and fp64 blocks, e_i, and per incidence
+// the tinc record, the triangle's hat gradients and A_T / 12 and the tangent
+// bases of the corner's two other vertices -- is loaded once by the whole
+// workgroup into lane-major 16-byte planes (a wave's ds_read_b128 of a plane
+// is 1 KiB of consecutive LDS) and read from there by every pair; only the
+// per-system operands (x64, I, f) stay global gathers. The arithmetic is
+// rcn_a2_term / rcn_tri_term's, the terms in the same slot and incidence
+// order, so r64 keeps its bits. Per-system partials: each wave's wave_sum goes
+// to a per-slice record and k_residual_fold adds a row block's four in
+// block_sum's order.
+//
+// Staged bytes of a slice of wa a2 slots and wt incidence slots (double2
+// units; res_staged_bytes, mof_pattern.cpp): E 3 planes, BLK 2 wa, INC 12 wt
+// {tinc | g0 g1 | g2 g3 | g4 g5 | g6 g7 | g8 w12 | ej x3 | ek x3}, then the wa
+// 4-byte column planes.
+//
+// 16 waves x 4 trips (C3, 1536 systems: 10.27 / 9.15 / 8.78 ms per launch at
+// 1 / 2 / 4 trips -- one workgroup per CU, so staging is not hidden and more
+// pairs per workgroup amortise it; 8 waves with deeper load batches 10.4-10.5
+// ms; profiles/res_lds/ab_levers.jsonl). Four a2 slots' gathers are issued
+// before the first use, but one incidence's at a time: two per load batch
+// need 68 B of scratch per lane at the 128 VGPRs a 1024-thread workgroup
+// leaves a wave (110 and none as written, the trip loop not unrolled).
+constexpr int kLdsW = 16, kLdsTrips = 4;
+constexpr int kLdsUA = 4;  // a2 slots per load batch
+constexpr int32_t kGrpResLds = 1;  // an XCD walks consecutive slices of one pair chunk
+constexpr int64_t kLdsFill = 1024;  // workgroups (4 per CU) below which a launch takes one trip per wave
+template <int NS, int W, int TRIPS>
+__global__ __launch_bounds__(64 * W) void k_residual_lds(OpArgs<double> op, int32_t nsl, int32_t B, RedArgs rd,
+                                                         const double *__restrict__ rhs,
+                                                         const double *__restrict__ x64,
+                                                         const int32_t *__restrict__ sysi,
+                                                         double *__restrict__ r64,
+                                                         double *__restrict__ spart) {
+    extern __shared__ double2 sm[];
+    constexpr int NT = 64 * W, PW = W * TRIPS;
+    const int32_t npair = (B + NS - 1) / NS;
+    int32_t s, chunk;
+    if (!xcd_map(nsl, (npair + PW - 1) / PW, s, chunk, kGrpResLds)) return;  // workgroup-uniform
+    const int32_t wv = threadIdx.x >> 6, l = threadIdx.x & 63;
+    // any active system in the chunk? Every wave reads the same flags, so the
+    // whole workgroup leaves here or nobody does (the barrier below).
+    {
+        bool any = false;
+        for (int32_t q = l; q < PW * NS; q += 64) {
+            const int32_t b = chunk * PW * NS + q;
+            any |= b < B && sysi[min(b, B - 1) * kSysStride + SI_ACTIVE] != 0;
+        }
+        if (__ballot(any) == 0) return;
+    }
+    const int32_t N = op.N;
+    const int32_t o = op.sell_off[s], wa = (op.sell_off[s + 1] - o) >> 6;
+    const int32_t to = op.tsell_off[s], wt = (op.tsell_off[s + 1] - to) >> 6;
+    double2 *const E = sm, *const BLK = sm + 3 * 64, *const INC = BLK + 2 * 64 * wa;
+    int32_t *const COL = reinterpret_cast<int32_t *>(INC + 12 * 64 * wt);
+    // ---- staging (all NT threads; lanes past N - 1 of the last slice stage
+    // the padding the tables hold for them and row N - 1's bases)
+    for (int32_t q = threadIdx.x; q < wa * 64; q += NT) {
+        const int32_t t = q >> 6, ll = q & 63;
+        COL[q] = op.sell_col[(int64_t)o + q];
+        const double2 *bp = reinterpret_cast<const double2 *>(op.a2s) + 2 * ((int64_t)o + q);
+        BLK[(2 * t) * 64 + ll] = bp[0];
+        BLK[(2 * t + 1) * 64 + ll] = bp[1];
+    }
+    for (int32_t q = threadIdx.x; q < 3 * 64; q += NT) {
+        const int32_t k = q >> 6, ll = q & 63;
+        E[q] = ld2(op.e + 6 * (int64_t)min(64 * s + ll, N - 1) + 2 * k);
+    }
+    for (int32_t q = threadIdx.x; q < wt * 4 * 64; q += NT) {
+        const int32_t ll = q & 63, part = (q >> 6) & 3, t = q >> 8;
+        const int4 e = op.tinc[(int64_t)to + t * 64 + ll];
+        double2 *P = INC + (12 * t) * 64 + ll;
+        if (part == 0) {
+            const double *g = op.gw + 9 * (int64_t)min(e.x, op.M - 1);
+            *reinterpret_cast<int4 *>(P) = e;
+            P[1 * 64] = make_double2(g[0], g[1]);
+            P[2 * 64] = make_double2(g[2], g[3]);
+            P[3 * 64] = make_double2(g[4], g[5]);
+        } else if (part == 1) {
+            const double *g = op.gw + 9 * (int64_t)min(e.x, op.M - 1);
+            P[4 * 64] = make_double2(g[6], g[7]);
+            P[5 * 64] = make_double2(g[8], op.w12[e.x]);
+        } else {
+            const double *ev = op.e + 6 * (int64_t)(part == 2 ? e.z : e.w);
+            double2 *Q = P + (part == 2 ? 6 : 9) * 64;
+            Q[0] = ld2(ev);
+            Q[64] = ld2(ev + 2);
+            Q[128] = ld2(ev + 4);
+        }
+    }
+    __syncthreads();  // the only barrier: nothing below may wait for another wave
+    // ---- compute: this wave's pairs
+    const int32_t i = 64 * s + l;
+#pragma unroll 1
+    for (int trip = 0; trip < TRIPS; ++trip) {
+        const int32_t bp = chunk * PW + trip * W + wv;
+        if (bp >= npair) break;
+        int32_t bs[NS];
+        bool act[NS], any = false;
+#pragma unroll
+        for (int t = 0; t < NS; ++t) {
+            bs[t] = min(NS * bp + t, B - 1);
+            act[t] = NS * bp + t < B && sysi[bs[t] * kSysStride + SI_ACTIVE] != 0;
+            any |= act[t];
+        }
+        if (!any) continue;
+        double v[2 * NS];  // rr, ff of each system
+#pragma unroll
+        for (int t = 0; t < 2 * NS; ++t) v[t] = 0.0;
+        if (i < N) {
+            double acc[NS][2];
+#pragma unroll
+            for (int t = 0; t < NS; ++t) acc[t][0] = acc[t][1] = 0.0;
+            // lambda a2 x, slots in order
+            for (int32_t t0 = 0; t0 < wa; t0 += kLdsUA) {
+                double2 xj[kLdsUA][NS];
+#pragma unroll
+                for (int u = 0; u < kLdsUA; ++u) {
+                    const int32_t j = COL[min(t0 + u, wa - 1) * 64 + l];
+#pragma unroll
+                    for (int t = 0; t < NS; ++t) xj[u][t] = ld2(x64 + 2 * ((int64_t)bs[t] * N + j));
+                }
+#pragma unroll
+                for (int u = 0; u < kLdsUA; ++u) {
+                    const int32_t tt = min(t0 + u, wa - 1);
+                    const double2 b0 = BLK[(2 * tt) * 64 + l], b1 = BLK[(2 * tt + 1) * 64 + l];
+                    const double blk[4] = {b0.x, b0.y, b1.x, b1.y};
+#pragma unroll
+                    for (int t = 0; t < NS; ++t) rcn_a2_term(blk, xj[u][t], t0 + u < wa, acc[t]);
+                }
+            }
+            // the row's own operands
+            double2 xi[NS];
+            double Ii[NS];
+#pragma unroll
+            for (int t = 0; t < NS; ++t) {
+                xi[t] = ld2(x64 + 2 * ((int64_t)bs[t] * N + i));
+                Ii[t] = op.I0[(int64_t)bs[t] * op.ldI + i];
+            }
+            const double2 e0 = E[l], e1 = E[64 + l], e2 = E[128 + l];
+            const double ei[6] = {e0.x, e0.y, e1.x, e1.y, e2.x, e2.y};
+            // the incident triangles in order
+            for (int32_t t0 = 0; t0 < wt; ++t0) {
+                const double2 *P = INC + (12 * t0) * 64 + l;
+                const int4 q = *reinterpret_cast<const int4 *>(P);
+                double Ij[NS], Ik[NS];
+                double2 xj[NS], xk[NS];
+#pragma unroll
+                for (int t = 0; t < NS; ++t) {
+                    const double *Ib = op.I0 + (int64_t)bs[t] * op.ldI;
+                    const int64_t vb = (int64_t)bs[t] * N;
+                    Ij[t] = Ib[q.z];
+                    Ik[t] = Ib[q.w];
+                    xj[t] = ld2(x64 + 2 * (vb + q.z));
+                    xk[t] = ld2(x64 + 2 * (vb + q.w));
+                }
+                const double2 g01 = P[64], g23 = P[2 * 64], g45 = P[3 * 64], g67 = P[4 * 64], g8w = P[5 * 64];
+                const double2 j0 = P[6 * 64], j1 = P[7 * 64], j2 = P[8 * 64];
+                const double2 k0 = P[9 * 64], k1 = P[10 * 64], k2 = P[11 * 64];
+                const double g[9] = {g01.x, g01.y, g23.x, g23.y, g45.x, g45.y, g67.x, g67.y, g8w.x};
+                const double ej[6] = {j0.x, j0.y, j1.x, j1.y, j2.x, j2.y};
+                const double ek[6] = {k0.x, k0.y, k1.x, k1.y, k2.x, k2.y};
+#pragma unroll
+                for (int t = 0; t < NS; ++t) {
+                    double val[2];
+                    rcn_tri_term(q.y, g, ei, ej, ek, g8w.y, Ii[t], Ij[t], Ik[t], xi[t], xj[t], xk[t], val);
+                    acc[t][0] += val[0];
+                    acc[t][1] += val[1];
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < NS; ++t)
+                rcn_out((int64_t)bs[t] * N + i, i < rd.nown, act[t], acc[t], rhs, r64, v[2 * t], v[2 * t + 1]);
+        }
+#pragma unroll
+        for (int t = 0; t < 2 * NS; ++t) v[t] = wave_sum(v[t]);
+        if (l == 0) {
+#pragma unroll
+            for (int t = 0; t < NS; ++t) {
+                if (!act[t]) continue;
+                double *op_ = spart + 2 * ((int64_t)bs[t] * nsl + s);
+                op_[0] = v[2 * t];
+                op_[1] = v[2 * t + 1];
+            }
+        }
+    }
+}
+// The (system, 256-row block) partial records from k_residual_lds's per-slice
+// ones: the block's four wave sums added as block_sum adds them, slices past
+// the last one counting 0.0 (as the waves past row N - 1 did).
+__global__ __launch_bounds__(kWG) void k_residual_fold(int32_t nsl, int32_t nblk, int32_t B, RedArgs rd,
+                                                       const int32_t *__restrict__ sysi,
+                                                       const double *__restrict__ spart,
+                                                       double *__restrict__ part) {
+    const int64_t q = (int64_t)blockIdx.x * kWG + threadIdx.x;
+    if (q >= (int64_t)B * nblk) return;
+    const int32_t b = (int32_t)(q / nblk), rb = (int32_t)(q - (int64_t)b * nblk);
+    if (!sysi[b * kSysStride + SI_ACTIVE]) return;
+    double w[4][2];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int32_t s = 4 * rb + k;
+        const double *p = spart + 2 * ((int64_t)b * nsl + min(s, nsl - 1));
+        w[k][0] = s < nsl ? p[0] : 0.0;
+        w[k][1] = s < nsl ? p[1] : 0.0;
+    }
+    double *out = part + 2 * red_rec(rd, B, b, rb);
+    out[0] = ((w[0][0] + w[1][0]) + w[2][0]) + w[3][0];
+    out[1] = ((w[0][1] + w[1][1]) + w[2][1]) + w[3][1];
 }
 
 // Max over all parts' max|d|, max|x64| records of system b (order-free).
@@ -1162,6 +1394,40 @@ MatArgs<V> make_mat(mof_mesh *m, const V *A) {
     return mt;
 }
 
+// The staged residual of a mesh whose widest slice fits kResLdsCap
+// (mesh_set_own): k_residual_lds into the per-slice records, then the fold.
+// The kernel's dynamic-LDS limit is raised once per process and device to
+// the fixed cap, never to a mesh's own size (a later, wider mesh would
+// otherwise launch past the limit an earlier one set).
+void launch_residual_lds(mof_mesh *m, const OpArgs<double> &op, int32_t nblk, int32_t B, hipStream_t s, RedArgs rd,
+                         const double *rhs, const double *x64, const int32_t *sysi, double *r64, double *part) {
+    constexpr int kMaxDev = 64;
+    static std::once_flag once[kMaxDev];
+    const auto kern = &k_residual_lds<kResNS, kLdsW, kLdsTrips>, kern1 = &k_residual_lds<kResNS, kLdsW, 1>;
+    MOF_REQUIRE(m->device >= 0 && m->device < kMaxDev, "device index out of range");
+    std::call_once(once[m->device], [&] {
+        for (const void *k : {reinterpret_cast<const void *>(kern), reinterpret_cast<const void *>(kern1)})
+            MOF_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kResLdsCap));
+    });
+    const int32_t nsl = m->pat.nslices, npair = (B + kResNS - 1) / kResNS;
+    // a small mesh or batch (fewer than kLdsFill workgroups at kLdsTrips pairs
+    // per wave) takes one pair per wave instead, so the launch still fills
+    // the CUs; a system's bits do not depend on the split
+    int32_t nchunk = (npair + kLdsW * kLdsTrips - 1) / (kLdsW * kLdsTrips);
+    const bool one = (int64_t)nsl * nchunk < kLdsFill && !g_force_residual_trips.load();
+    if (one) nchunk = (npair + kLdsW - 1) / kLdsW;
+    MOF_REQUIRE(m->res_lds_bytes <= kResLdsCap && m->ws.res_spart.n >= (size_t)2 * nsl * B,
+                "staged residual: workspace not set up");
+    const unsigned grid = xcd_grid(nsl, nchunk, kGrpResLds);
+    MOF_REQUIRE((int64_t)grid * 64 * kLdsW < ((int64_t)1 << 32), "launch grid past 2^32 work-items");
+    g_residual_launches[one ? 1 : 2]++;
+    (one ? kern1 : kern)<<<dim3(grid), 64 * kLdsW, (size_t)m->res_lds_bytes, s>>>(op, nsl, B, rd, rhs, x64, sysi, r64,
+                                                                                   m->ws.res_spart.p);
+    const int64_t nrec = (int64_t)B * nblk;
+    k_residual_fold<<<dim3((unsigned)((nrec + kWG - 1) / kWG)), kWG, 0, s>>>(nsl, nblk, B, rd, sysi,
+                                                                             m->ws.res_spart.p, part);
+}
+
 // r64 = f - A x64 of the batch: from the u64 the fp64 path / recovery
 // stored, or with u re-formed from the I rows (two systems per thread).
 // Measured and not kept (round 3, profiles/r03_ab/a64_*): the row assembly
@@ -1174,9 +1440,13 @@ void launch_residual(mof_mesh *m, int32_t nblk, int32_t B, hipStream_t s, RedArg
     const OpArgs<double> op = op64(m);
     if (op.u)
         k_residual<<<dim3(xcd_grid(nblk, B, kGrpRes)), kWG, 0, s>>>(op, nblk, B, rd, args...);
-    else
+    else if (m->res_lds)
+        launch_residual_lds(m, op, nblk, B, s, rd, args...);
+    else {
+        g_residual_launches[0]++;
         k_residual_rcn<kResNS><<<dim3(xcd_grid(nblk, (B + kResNS - 1) / kResNS, kGrpRes)), kWG, 0, s>>>(
             op, nblk, B, rd, args...);
+    }
 }
 
 template <typename V>
@@ -1645,6 +1915,7 @@ void ensure_workspace(mof_mesh *m, int32_t B, uint32_t precision) {
     w.sc.alloc((size_t)6 * B);
     w.sc.zero(m->stream);
     w.part_rr0.alloc((size_t)2 * w.nblk * B);
+    if (m->res_lds) w.res_spart.alloc((size_t)2 * m->pat.nslices * B);
     w.part_dx.alloc((size_t)2 * ((N + kWG - 1) / kWG) * B);
     w.sysd.alloc((size_t)kSysStride * B);
     w.sysi.alloc((size_t)kSysStride * B);

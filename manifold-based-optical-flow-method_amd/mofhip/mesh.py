@@ -329,3 +329,53 @@ class force_index32:
     def __exit__(self, *exc):
         L.check(L.lib().mof_test_force_index32(0))
         return False
+
+
+def residual_probe(triangles, n_vertices: int, reorder: bool = True) -> dict:
+    """Host-only diagnostic (mof_residual_probe): ``staged_bytes``, the LDS
+    the staged fp64 residual (k_residual_lds) needs for the widest 64-row
+    slice of this triangle list -- 64 (36 a2 slots + 192 incidence slots +
+    48) bytes -- and ``staged_used``, whether a handle of the mesh takes that
+    kernel (the bytes fit the kernel's fixed LDS limit). The batch plays no
+    part."""
+    T = np.ascontiguousarray(triangles, dtype=np.int32)
+    flags = 0 if reorder else L.MOF_NO_REORDER
+    nb, used = ctypes.c_int64(0), ctypes.c_int32(0)
+    L.check(L.lib().mof_residual_probe(L.ptr(T), int(n_vertices), len(T), flags, ctypes.byref(nb),
+                                       ctypes.byref(used)))
+    return {"staged_bytes": int(nb.value), "staged_used": bool(used.value)}
+
+
+class force_residual_rows:
+    """Tests only (mof_test_force_residual_rows): handles created inside the
+    block keep the row kernel k_residual_rcn where the staged one would fit."""
+
+    def __enter__(self):
+        L.check(L.lib().mof_test_force_residual_rows(1))
+        return self
+
+    def __exit__(self, *exc):
+        L.check(L.lib().mof_test_force_residual_rows(0))
+        return False
+
+
+class force_residual_trips:
+    """Tests only (mof_test_force_residual_trips): every staged residual launch
+    inside the block takes the four-trip kernel of the large launches."""
+
+    def __enter__(self):
+        L.check(L.lib().mof_test_force_residual_trips(1))
+        return self
+
+    def __exit__(self, *exc):
+        L.check(L.lib().mof_test_force_residual_trips(0))
+        return False
+
+
+def residual_launches() -> dict:
+    """Tests only (mof_test_residual_launches): launches so far in this process
+    of the fp64 residual's row kernel (``rows``) and of the staged kernel with
+    one (``staged_one``) and four (``staged_multi``) trips per wave."""
+    c = np.zeros(3, dtype=np.int64)
+    L.check(L.lib().mof_test_residual_launches(L.ptr(c)))
+    return {"rows": int(c[0]), "staged_one": int(c[1]), "staged_multi": int(c[2])}
