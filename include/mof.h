@@ -449,6 +449,40 @@ int mof_test_force_residual_trips(int32_t on);
  * really ran, whatever the probe says. */
 int mof_test_residual_launches(int64_t *counts);
 
+/* Diagnostic (host only): the staged mixed-precision row assembly keeps, per
+ * 64-row slice of the internal vertex order, what every system reads alike in
+ * LDS: 64 x (112 B per incidence slot + 48 B per a2 slot + 48 B).
+ * *staged_bytes: the largest slice of the mesh given by tri (M x 3) over N
+ * vertices, laid out as mof_mesh_create lays it out (flags: MOF_NO_REORDER);
+ * *staged_used (may be NULL): no row is wider than 8 blocks and the bytes fit
+ * the kernel's fixed 160 KiB limit, so a handle of the mesh takes the staged
+ * kernel -- otherwise the row kernel. The batch plays no part. */
+int mof_assembly_probe(const int32_t *tri, int32_t N, int32_t M, uint32_t flags, int64_t *staged_bytes,
+                       int32_t *staged_used);
+/* Test hook (never read from the environment): every mesh and decomposed part
+ * created after mof_test_force_assembly_rows(1) keeps the row kernel of the
+ * mixed-precision assembly even where the staged one fits (0: back to the
+ * default) -- the staged kernel's results are compared with it bit for bit. */
+int mof_test_force_assembly_rows(int32_t on);
+/* Test hook: small launches of the staged assembly run one system per wave,
+ * large ones (the flagship's) several in turn; after
+ * mof_test_force_assembly_trips(1) every staged launch takes the multi-trip
+ * kernel, so small meshes exercise it (0: back to the default). */
+int mof_test_force_assembly_trips(int32_t on);
+/* Test hook: counts[0..2] = launches so far in this process of the row
+ * assembly kernel, of the staged kernel with one trip per wave and of the
+ * staged kernel with several. */
+int mof_test_assembly_launches(int64_t *counts);
+/* Test hook: a plain device-to-host copy of what the last mixed-precision
+ * assembly on this handle left in the workspace for its system `system`:
+ * A32 (4 floats per SELL position), A0h (the multigrid's bf16 copy, 8 bytes
+ * per SELL position; *have_A0h = 0 and untouched when the handle has no
+ * multigrid storage) and rhs (2 N doubles), in the internal order. Positions
+ * the assembly never writes (padding, transposed lower blocks) hold whatever
+ * the allocation held. Any output may be NULL. */
+int mof_test_assembly_readback(mof_mesh *mesh, int32_t system, float *A32, void *A0h, double *rhs,
+                               int32_t *have_A0h);
+
 /* Diagnostic (host only): checks that the XCD-aware workgroup order of the
  * row kernels -- nblk row blocks x batch systems, walked in groups of
  * `group` systems (0: all) -- visits every (row block, system) pair exactly

@@ -450,6 +450,17 @@ std::atomic<int> g_force_index32{0};
 std::atomic<int> g_force_residual_rows{0};
 std::atomic<int> g_force_residual_trips{0};
 std::atomic<int64_t> g_residual_launches[3];
+std::atomic<int> g_force_assembly_rows{0};
+std::atomic<int> g_force_assembly_trips{0};
+std::atomic<int64_t> g_assembly_launches[3];
+
+void raise_lds_limit(LdsLimit &st, int device, std::initializer_list<const void *> kernels, int64_t cap) {
+    MOF_REQUIRE(device >= 0 && device < LdsLimit::kMaxDev, "device index out of range");
+    std::call_once(st.once[device], [&] {
+        for (const void *k : kernels)
+            MOF_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap));
+    });
+}
 
 void mesh_set_own(mof_mesh *m, int32_t nown) {
     MOF_HIP(hipSetDevice(m->device));
@@ -486,6 +497,8 @@ void mesh_set_own(mof_mesh *m, int32_t nown) {
     }
     m->res_lds_bytes = res_staged_bytes(m->pat);
     m->res_lds = m->res_lds_bytes <= kResLdsCap && !g_force_residual_rows.load();
+    m->asm_lds_bytes = asm_staged_bytes(m->pat);
+    m->asm_lds = asm_staged_fits(m->pat) && !g_force_assembly_rows.load();
     int64_t own = 0;  // positions read at their own place: diagonal + upper blocks
     for (int32_t v : mir) own += v >= 0 && !(v & kMirT);
     m->blocks_read = own;
@@ -1293,6 +1306,55 @@ int mof_test_residual_launches(int64_t *counts) {
     return guarded([&] {
         MOF_REQUIRE(counts, "NULL argument");
         for (int k = 0; k < 3; ++k) counts[k] = mof::g_residual_launches[k].load();
+    });
+}
+
+int mof_assembly_probe(const int32_t *tri, int32_t N, int32_t M, uint32_t flags, int64_t *staged_bytes,
+                       int32_t *staged_used) {
+    return guarded([&] {
+        MOF_REQUIRE(tri && staged_bytes && N > 0 && M > 0, "bad arguments");
+        mof_mesh m;  // the internal order and pattern of mof_mesh_create (host half only)
+        const std::vector<double> zero(3 * (size_t)std::max(N, M), 0.0);
+        mof::mesh_prepare_host(&m, zero.data(), zero.data(), tri, zero.data(), N, M, flags, nullptr, nullptr);
+        *staged_bytes = mof::asm_staged_bytes(m.pat);
+        if (staged_used) *staged_used = mof::asm_staged_fits(m.pat);
+    });
+}
+
+int mof_test_force_assembly_rows(int32_t on) {
+    return guarded([&] { mof::g_force_assembly_rows.store(on != 0); });
+}
+
+int mof_test_force_assembly_trips(int32_t on) {
+    return guarded([&] { mof::g_force_assembly_trips.store(on != 0); });
+}
+
+int mof_test_assembly_launches(int64_t *counts) {
+    return guarded([&] {
+        MOF_REQUIRE(counts, "NULL argument");
+        for (int k = 0; k < 3; ++k) counts[k] = mof::g_assembly_launches[k].load();
+    });
+}
+
+int mof_test_assembly_readback(mof_mesh *m, int32_t system, float *A32, void *A0h, double *rhs, int32_t *have_A0h) {
+    return guarded([&] {
+        MOF_REQUIRE(m, "mesh is NULL");
+        DeviceGuard dg(m->device);
+        mof::mesh_join_prep(m);
+        const mof::Workspace &w = m->ws;
+        const size_t nb = (size_t)m->pat.sell_nb(), b = (size_t)system;
+        MOF_REQUIRE(system >= 0 && system < w.JB && w.A32.n >= 4 * nb * (b + 1) &&
+                        w.rhs.n >= 2 * (size_t)m->N * (b + 1),
+                    "no mixed-precision assembly of that system in the workspace");
+        MOF_HIP(hipStreamSynchronize(m->stream));
+        if (A32) MOF_HIP(hipMemcpy(A32, w.A32.p + 4 * nb * b, 4 * nb * sizeof(float), hipMemcpyDeviceToHost));
+        if (rhs)
+            MOF_HIP(hipMemcpy(rhs, w.rhs.p + 2 * (size_t)m->N * b, 2 * (size_t)m->N * sizeof(double),
+                              hipMemcpyDeviceToHost));
+        const void *h = m->amg ? mof::amg_fine(m).A0h : nullptr;
+        if (have_A0h) *have_A0h = h != nullptr;
+        if (A0h && h)
+            MOF_HIP(hipMemcpy(A0h, static_cast<const uint2 *>(h) + nb * b, nb * sizeof(uint2), hipMemcpyDeviceToHost));
     });
 }
 

@@ -2137,12 +2137,13 @@ bool amg_build(mof_mesh *m) {
                 if (knob(Knob::Verbose))
                     std::fprintf(stderr, "mof amg: boundary sweeps x%d on a ring of %d rows (%d outside, %lld B of LDS)\n",
                                  G.bsw_sweeps, nbr, G.bsw_nout, (long long)lds);
-                if (lds > 64 * 1024) {
-                    MOF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bsweep<true>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    MOF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bsweep<false>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                }
+                // the fixed cap, never this ring's own size: a later mesh's smaller
+                // ring must not lower the limit under this mesh's launches
+                static LdsLimit limit;
+                raise_lds_limit(limit, m->device,
+                                {reinterpret_cast<const void *>(&k_bsweep<true>),
+                                 reinterpret_cast<const void *>(&k_bsweep<false>)},
+                                kBswLdsMax);
             }
         }
     }

@@ -439,6 +439,37 @@ __global__ __launch_bounds__(kWG) void k_assemble_mixed(
     *reinterpret_cast<double2 *>(rhs + 2 * vi) = make_double2(f0, f1);
 }
 
+// One stored slot of row i of one system: the fp32 block (+ lambda a2), its
+// bf16 copy (the identity on a decomposed part's ghost rows and columns) and,
+// with the diagonal block, its inverse and f_i. Shared by the row and the
+// staged kernel.
+__device__ __forceinline__ void row_slot_store(const float (&acc)[4], float4 s4, bool diag, bool ghost, int64_t qq,
+                                               int64_t vi, double f0, double f1, int block_jacobi,
+                                               float *__restrict__ A, float *__restrict__ dinv32,
+                                               double *__restrict__ rhs, uint2 *__restrict__ Ah) {
+    const float Av[4] = {acc[0] + s4.x, acc[1] + s4.y, acc[2] + s4.z, acc[3] + s4.w};
+    reinterpret_cast<float4 *>(A)[qq] = make_float4(Av[0], Av[1], Av[2], Av[3]);
+    if (Ah) {
+        if (ghost)
+            h0_st(Ah, qq, diag ? 1.f : 0.f, 0.f, 0.f, diag ? 1.f : 0.f);
+        else
+            h0_st(Ah, qq, Av[0], Av[1], Av[2], Av[3]);
+    }
+    if (!diag) return;
+    double inv[4];
+    const double d0 = Av[0], d1 = Av[1], d2 = Av[2], d3 = Av[3];
+    if (block_jacobi) {
+        const double det = d0 * d3 - d1 * d2;
+        inv[0] = d3 / det; inv[1] = -d1 / det; inv[2] = -d2 / det; inv[3] = d0 / det;
+    } else {
+        inv[0] = 1.0 / d0; inv[1] = 0.0; inv[2] = 0.0; inv[3] = 1.0 / d3;
+    }
+    if (!Ah)  // multigrid: the smoother's D comes from the bf16 diagonal blocks
+        reinterpret_cast<float4 *>(dinv32)[vi] =
+            make_float4((float)inv[0], (float)inv[1], (float)inv[2], (float)inv[3]);
+    *reinterpret_cast<double2 *>(rhs + 2 * vi) = make_double2(f0, f1);
+}
+
 // Row i's stores of one system: A blocks (+ lambda a2), the bf16 copies,
 // the diagonal block's inverse and f_i.
 template <int WMAX>
@@ -455,31 +486,9 @@ __device__ __forceinline__ void rows_store(const float (&acc)[WMAX][4], double f
         // symmetric layout: lower blocks are read as transposed upper
         // ones and never leave the registers
         if (mir && (mir[pos] & kMirT)) continue;
-        const int64_t qq = (int64_t)b * sell_nb + pos;
-        const float4 s4 = reinterpret_cast<const float4 *>(a2s)[pos];
-        const float Av[4] = {acc[z][0] + s4.x, acc[z][1] + s4.y, acc[z][2] + s4.z, acc[z][3] + s4.w};
-        reinterpret_cast<float4 *>(A)[qq] = make_float4(Av[0], Av[1], Av[2], Av[3]);
-        if (Ah) {
-            const bool g = i >= nown || sell_col[pos] >= nown;
-            if (g)
-                h0_st(Ah, qq, z == 0 ? 1.f : 0.f, 0.f, 0.f, z == 0 ? 1.f : 0.f);
-            else
-                h0_st(Ah, qq, Av[0], Av[1], Av[2], Av[3]);
-        }
-        if (z != 0) continue;
-        double inv[4];
-        const double d0 = Av[0], d1 = Av[1], d2 = Av[2], d3 = Av[3];
-        if (block_jacobi) {
-            const double det = d0 * d3 - d1 * d2;
-            inv[0] = d3 / det; inv[1] = -d1 / det; inv[2] = -d2 / det; inv[3] = d0 / det;
-        } else {
-            inv[0] = 1.0 / d0; inv[1] = 0.0; inv[2] = 0.0; inv[3] = 1.0 / d3;
-        }
-        const int64_t vi = (int64_t)b * N + i;
-        if (!Ah)  // multigrid: the smoother's D comes from the bf16 diagonal blocks
-            reinterpret_cast<float4 *>(dinv32)[vi] =
-                make_float4((float)inv[0], (float)inv[1], (float)inv[2], (float)inv[3]);
-        *reinterpret_cast<double2 *>(rhs + 2 * vi) = make_double2(f0, f1);
+        const bool g = Ah && (i >= nown || sell_col[pos] >= nown);
+        row_slot_store(acc[z], reinterpret_cast<const float4 *>(a2s)[pos], z == 0, g, (int64_t)b * sell_nb + pos,
+                       (int64_t)b * N + i, f0, f1, block_jacobi, A, dinv32, rhs, Ah);
     }
 }
 
@@ -512,7 +521,24 @@ struct TriGeo {
 // fold of the same operator, rounded differently; f keeps its bits). C3,
 // B = 512, rocprof on one box (profiles/r04_ab/call1b/): 9047-9163 -> 8630 us
 // per launch against the round-3 per-incidence 2x2 fold.
-// g3_store: the slots' blocks E_i G E_j^T + lambda a2, then rows_store's stores.
+// g3_slot: one slot's block E_i G E_j^T (fp32; G = [xx xy xz; xy yy yz; xz yz zz]),
+// shared by the row and the staged kernel; g3_project: the stored slots of a row.
+__device__ __forceinline__ void g3_slot(const float (&g)[6], const float (&eif)[6], const float (&ej)[6],
+                                        float (&acc)[4]) {
+    float H[3][2];  // H = G E_j^T (3 x 2)
+#pragma unroll
+    for (int be = 0; be < 2; ++be) {
+        const float *v = ej + 3 * be;
+        H[0][be] = g[0] * v[0] + g[1] * v[1] + g[2] * v[2];
+        H[1][be] = g[1] * v[0] + g[3] * v[1] + g[4] * v[2];
+        H[2][be] = g[2] * v[0] + g[4] * v[1] + g[5] * v[2];
+    }
+#pragma unroll
+    for (int al = 0; al < 2; ++al)
+#pragma unroll
+        for (int be = 0; be < 2; ++be)
+            acc[2 * al + be] = eif[3 * al] * H[0][be] + eif[3 * al + 1] * H[1][be] + eif[3 * al + 2] * H[2][be];
+}
 template <int WMAX>
 __device__ __forceinline__ void g3_project(const float (&G)[WMAX][6], const double (&ei)[6], int32_t deg, int64_t o,
                                            const int32_t *__restrict__ sell_col, const double *__restrict__ e,
@@ -530,21 +556,48 @@ __device__ __forceinline__ void g3_project(const float (&G)[WMAX][6], const doub
         float ej[6];
 #pragma unroll
         for (int k = 0; k < 6; ++k) ej[k] = (float)e[6 * (int64_t)j + k];
-        // G = [xx xy xz; xy yy yz; xz yz zz]; H = G E_j^T (3 x 2)
-        const float *g = G[z];
-        float H[3][2];
+        g3_slot(G[z], eif, ej, acc[z]);
+    }
+}
+// One incidence of row i of one system (corner c of its triangle, the other
+// two corners vj, vk with the row's slots sl = sj | sk << 8): grad_M I in
+// k_tri_step's arithmetic, the row's f term (real: not a padding incidence)
+// and the outer product folded into the slots' G. Shared by the row and the
+// staged kernel; aj / ak and bj / bk are I0 and I1 at vj / vk.
+template <int WMAX>
+__device__ __forceinline__ void asm_inc_term(int32_t i, bool real, int32_t c, int32_t vj, int32_t vk, int32_t sl,
+                                             const double (&g)[9], double At, float wv, const double (&ei)[6],
+                                             double Ii0, double pdi, double aj, double ak, double bj, double bk,
+                                             double hb, double &f0, double &f1, float (&G)[WMAX][6]) {
+    const int32_t sj = sl & 0xff, sk = sl >> 8;
+    // set(T) - {i} in corner order: at most 2 distinct other corners
+    const bool hj = vj != i, hk = vk != i && vk != vj;
+    const double pdj = (bj - aj) / hb, pdk = (bk - ak) / hb;
+    // the triangle's I0 in its own corner order (corner c is i)
+    const double c0 = c == 0 ? Ii0 : (c == 1 ? ak : aj);
+    const double c1 = c == 0 ? aj : (c == 1 ? Ii0 : ak);
+    const double c2 = c == 0 ? ak : (c == 1 ? aj : Ii0);
+    double gI[3];
 #pragma unroll
-        for (int be = 0; be < 2; ++be) {
-            const float *v = ej + 3 * be;
-            H[0][be] = g[0] * v[0] + g[1] * v[1] + g[2] * v[2];
-            H[1][be] = g[1] * v[0] + g[3] * v[1] + g[4] * v[2];
-            H[2][be] = g[2] * v[0] + g[4] * v[1] + g[5] * v[2];
-        }
+    for (int d = 0; d < 3; ++d) gI[d] = (c0 * g[d] + c1 * g[3 + d]) + c2 * g[6 + d];
+    const double ui0 = dot64(gI, ei), ui1 = dot64(gI, ei + 3);
+    const double po = hj ? (hk ? pdj + pdk : pdj) : (hk ? pdk : 0.0);
+    if (real) {  // f in the reference's triangle order
+        f0 += ui0 * (2 * pdi + po) * At / 12;
+        f1 += ui1 * (2 * pdi + po) * At / 12;
+    }
+    // the a1 terms (compute_a1's (u_i^a u_j^b) w) as one outer product
+    // of grad_M I per incidence, weighted per slot: A/6 = 2 A/12 on the
+    // diagonal block (a degenerate triangle's second corner at i
+    // included), A/12 on the blocks of the other two corners
+    const float wd = wv + wv, wj = sj == 0 ? wd : wv, wk = sk == 0 ? wd : wv;
+    const float gx = (float)gI[0], gy = (float)gI[1], gz = (float)gI[2];
+    const float op[6] = {gx * gx, gx * gy, gx * gz, gy * gy, gy * gz, gz * gz};
 #pragma unroll
-        for (int al = 0; al < 2; ++al)
+    for (int z = 0; z < WMAX; ++z) {
+        const float cz = (z == 0 ? wd : 0.f) + (z == sj ? wj : 0.f) + (z == sk ? wk : 0.f);
 #pragma unroll
-            for (int be = 0; be < 2; ++be)
-                acc[z][2 * al + be] = eif[3 * al] * H[0][be] + eif[3 * al + 1] * H[1][be] + eif[3 * al + 2] * H[2][be];
+        for (int x = 0; x < 6; ++x) G[z][x] = __builtin_fmaf(cz, op[x], G[z][x]);
     }
 }
 // WMAX = 8 at 4 waves per SIMD (128 VGPRs, no scratch; 130 and 3 waves
@@ -585,49 +638,171 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(WMAX <= 8 ?
             const int64_t e = (int64_t)to + (int64_t)t * kSlice + l;
             const int4 q = tinc[e];
             const int32_t sl = tslot[e];
-            const bool real = q.x < M;  // padding (T = M): weight 0, no f term
-            const int64_t T = min(q.x, M - 1);
-            const int32_t c = q.y, vj = q.z, vk = q.w;
+            const int64_t T = min(q.x, M - 1);  // padding (T = M): weight 0, no f term
             double g[9];
 #pragma unroll
             for (int k = 0; k < 9; ++k) g[k] = geo.gw[9 * T + k];
             const double At = geo.area[T];
             const float wv = w12[q.x];
-            const int32_t sj = sl & 0xff, sk = sl >> 8;
-            // set(T) - {i} in corner order: at most 2 distinct other corners
-            const bool hj = vj != i, hk = vk != i && vk != vj;
+            const int32_t vj = q.z, vk = q.w;
             const double aj = I0b[vj], ak = I0b[vk];
-            const double pdj = (I1b[vj] - aj) / hb, pdk = (I1b[vk] - ak) / hb;
-            // the triangle's I0 in its own corner order (corner c is i)
-            const double c0 = c == 0 ? Ii0 : (c == 1 ? ak : aj);
-            const double c1 = c == 0 ? aj : (c == 1 ? Ii0 : ak);
-            const double c2 = c == 0 ? ak : (c == 1 ? aj : Ii0);
-            double gI[3];
-#pragma unroll
-            for (int d = 0; d < 3; ++d) gI[d] = (c0 * g[d] + c1 * g[3 + d]) + c2 * g[6 + d];
-            const double ui0 = dot64(gI, ei), ui1 = dot64(gI, ei + 3);
-            const double po = hj ? (hk ? pdj + pdk : pdj) : (hk ? pdk : 0.0);
-            if (real) {  // f in the reference's triangle order
-                f0 += ui0 * (2 * pdi + po) * At / 12;
-                f1 += ui1 * (2 * pdi + po) * At / 12;
-            }
-            // the a1 terms (compute_a1's (u_i^a u_j^b) w) as one outer product
-            // of grad_M I per incidence, weighted per slot: A/6 = 2 A/12 on the
-            // diagonal block (a degenerate triangle's second corner at i
-            // included), A/12 on the blocks of the other two corners
-            const float wd = wv + wv, wj = sj == 0 ? wd : wv, wk = sk == 0 ? wd : wv;
-            const float gx = (float)gI[0], gy = (float)gI[1], gz = (float)gI[2];
-            const float op[6] = {gx * gx, gx * gy, gx * gz, gy * gy, gy * gz, gz * gz};
-#pragma unroll
-            for (int z = 0; z < WMAX; ++z) {
-                const float cz = (z == 0 ? wd : 0.f) + (z == sj ? wj : 0.f) + (z == sk ? wk : 0.f);
-#pragma unroll
-                for (int x = 0; x < 6; ++x) G[z][x] = __builtin_fmaf(cz, op[x], G[z][x]);
-            }
+            asm_inc_term<WMAX>(i, q.x < M, q.y, vj, vk, sl, g, At, wv, ei, Ii0, pdi, aj, ak, I1b[vj], I1b[vk], hb, f0,
+                               f1, G);
         }
         g3_project<WMAX>(G, ei, vptr[i + 1] - vptr[i], sell_off[s] + l, sell_col, geo.e, mir, acc);
         rows_store<WMAX>(acc, f0, f1, i, b, N, vptr[i + 1] - vptr[i], sell_off[s] + l, sell_nb, sell_col, a2s,
                          block_jacobi, A, dinv32, rhs, Ah, nown, mir);
+    }
+}
+
+// The row assembly with a row slice's geometry staged in LDS (the shape of
+// k_residual_lds, mof_pcg.hip): a workgroup is one SELL-64 slice x W waves,
+// lane l of every wave is row 64 s + l, and wave w takes the systems
+// chunk (W TRIPS) + trip W + w, one system per thread. What
+// k_assemble_rows_rc requests per row and system and that is the same for
+// every system -- per incidence the tinc record, the triangle's hat gradients,
+// A_T, A_T / 12 and the slot word; per a2 slot the column's tangent bases
+// (already floats), the lambda a2 block and whether the slot is stored and is a
+// ghost's; the row's own bases -- is loaded once by the whole workgroup into
+// lane-major 16-byte planes and read from there by every system; only I0 / I1
+// at the row and its incidences' corners and dt[b] stay global loads. The
+// arithmetic is asm_inc_term / g3_slot / row_slot_store's, the incidences and
+// slots in the row kernel's order, so A32, A0h, dinv32 and rhs keep their bits.
+//
+// Staged planes of a slice of wt incidence slots and wa a2 slots
+// (asm_slice_bytes, mof_internal.h): E 3 planes; INC 7 wt {tinc | g0 g1 |
+// g2 g3 | g4 g5 | g6 g7 | g8 A_T | w12 tslot - -}; SLT 3 wa {flags e_j[0..2] |
+// e_j[3..5] - | lambda a2}. Flags: 1 = stored (a block of the row, not a
+// transposed lower one), 2 = ghost row or column (its bf16 copy is the identity).
+//
+// 8 waves x 8 trips (C3, 1536 systems, per launch; profiles/asm_lds/
+// ab_levers.jsonl): 16 waves at 2 / 4 / 8 trips 17.06 / 16.09 / 15.30 ms, 8
+// waves at 4 / 8 / 12 / 16 trips 15.74 / 15.03-14.85 / 14.58 / 14.89 ms against
+// k_assemble_rows_rc<8>'s 24.7 ms. A C3 slice stages 66 KiB, so two 512-thread
+// workgroups share a CU and one stages while the other computes; more trips
+// amortise the staging. 126 VGPRs, no scratch, with the wave's number read as a
+// scalar (its system's I rows and dt in SGPRs; 128 and 20 B of scratch
+// without) and the trip loop not unrolled. Not run: the next incidence's tinc
+// record and I gathers loaded one iteration ahead (128 VGPRs, 52 B of scratch).
+// -D overrides for A/B builds (tools/build_variant.sh; profiles/asm_lds/ab_levers.jsonl)
+#ifndef MOF_ASM_LDS_W
+#define MOF_ASM_LDS_W 8
+#endif
+#ifndef MOF_ASM_LDS_TRIPS
+#define MOF_ASM_LDS_TRIPS 8
+#endif
+#ifndef MOF_ASM_LDS_FILL
+#define MOF_ASM_LDS_FILL 1024
+#endif
+constexpr int kAsmLdsW = MOF_ASM_LDS_W, kAsmLdsTrips = MOF_ASM_LDS_TRIPS;
+constexpr int32_t kGrpAsmLds = 1;      // an XCD walks consecutive slices of one system chunk
+// workgroups (two rounds of 2 per CU) below which a launch takes one trip per wave: C1's 11 slices
+// x 15 systems (mixed precision) 20.5 us at one trip, 32.5 us with the multi-trip instance, 20.0 us
+// with the row kernel
+constexpr int64_t kAsmLdsFill = MOF_ASM_LDS_FILL;
+template <int W, int TRIPS>
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))) void k_assemble_lds(
+    int32_t N, int32_t M, int32_t nsl, int32_t B, int64_t sell_nb, const int32_t *__restrict__ sell_off,
+    const int32_t *__restrict__ sell_col, const int32_t *__restrict__ vptr, const int32_t *__restrict__ tsell_off,
+    const int4 *__restrict__ tinc, const int32_t *__restrict__ tslot, const float *__restrict__ w12,
+    const float *__restrict__ a2s, int block_jacobi, float *__restrict__ A, float *__restrict__ dinv32,
+    double *__restrict__ rhs, uint2 *__restrict__ Ah, int32_t nown, const int32_t *__restrict__ mir, TriGeo geo) {
+    extern __shared__ double2 asm_lds[];
+    constexpr int NT = 64 * W, PW = W * TRIPS, WMAX = kAsmLdsMaxW;
+    int32_t s, chunk;
+    if (!xcd_map(nsl, (B + PW - 1) / PW, s, chunk, kGrpAsmLds)) return;  // workgroup-uniform
+    // the wave's number as a scalar: its system, I rows and dt stay in SGPRs
+    const int32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l = threadIdx.x & 63;
+    const int32_t o = sell_off[s], wa = (sell_off[s + 1] - o) >> 6;
+    const int32_t to = tsell_off[s], wt = (tsell_off[s + 1] - to) >> 6;
+    double2 *const E = asm_lds, *const INC = asm_lds + 3 * 64, *const SLT = INC + 7 * 64 * wt;
+    // ---- staging (all NT threads; lanes past N - 1 of the last slice stage
+    // the padding the tables hold for them, row N - 1's bases and no stored slot)
+    for (int32_t q = threadIdx.x; q < 3 * 64; q += NT) {
+        const int32_t k = q >> 6, ll = q & 63;
+        E[q] = *reinterpret_cast<const double2 *>(geo.e + 6 * (int64_t)min(64 * s + ll, N - 1) + 2 * k);
+    }
+    for (int32_t q = threadIdx.x; q < wt * 2 * 64; q += NT) {
+        const int32_t ll = q & 63, part = (q >> 6) & 1, t = q >> 7;
+        const int64_t e = (int64_t)to + t * 64 + ll;
+        const int4 r = tinc[e];
+        const int64_t T = min(r.x, M - 1);  // padding (T = M): weight w12[M] = 0, no f term
+        const double *g = geo.gw + 9 * T;
+        double2 *P = INC + (7 * t) * 64 + ll;
+        if (part == 0) {
+            *reinterpret_cast<int4 *>(P) = r;
+            P[1 * 64] = make_double2(g[0], g[1]);
+            P[2 * 64] = make_double2(g[2], g[3]);
+            P[3 * 64] = make_double2(g[4], g[5]);
+        } else {
+            P[4 * 64] = make_double2(g[6], g[7]);
+            P[5 * 64] = make_double2(g[8], geo.area[T]);
+            *reinterpret_cast<int4 *>(P + 6 * 64) = make_int4(__float_as_int(w12[r.x]), tslot[e], 0, 0);
+        }
+    }
+    for (int32_t q = threadIdx.x; q < wa * 64; q += NT) {
+        const int32_t z = q >> 6, ll = q & 63, i = 64 * s + ll;
+        const int64_t pos = (int64_t)o + q;
+        const int32_t j = sell_col[pos];
+        const int32_t deg = i < N ? vptr[i + 1] - vptr[i] : 0;
+        int32_t fl = 0;
+        if (z < deg && !(mir && (mir[pos] & kMirT))) fl |= 1;
+        if (i >= nown || j >= nown) fl |= 2;
+        const double *ej = geo.e + 6 * (int64_t)min(j, N - 1);
+        float4 *S = reinterpret_cast<float4 *>(SLT + (3 * z) * 64 + ll);
+        S[0] = make_float4(__int_as_float(fl), (float)ej[0], (float)ej[1], (float)ej[2]);
+        S[64] = make_float4((float)ej[3], (float)ej[4], (float)ej[5], 0.f);
+        S[128] = reinterpret_cast<const float4 *>(a2s)[pos];
+    }
+    __syncthreads();  // the only barrier: nothing below may wait for another wave
+    // ---- compute: this wave's systems
+    const int32_t i = 64 * s + l;
+    if (i >= N) return;
+    const double2 e0 = E[l], e1 = E[64 + l], e2 = E[128 + l];
+    const double ei[6] = {e0.x, e0.y, e1.x, e1.y, e2.x, e2.y};
+#pragma unroll 1
+    for (int trip = 0; trip < TRIPS; ++trip) {
+        const int32_t b = chunk * PW + trip * W + wv;
+        if (b >= B) break;
+        const double *I0b = geo.J0 + (int64_t)b * N, *I1b = geo.J1 + (int64_t)b * N;
+        const double hb = geo.dt[b];
+        float G[WMAX][6];  // the slots' 3x3 a1 sums (symmetric: xx xy xz yy yz zz)
+#pragma unroll
+        for (int z = 0; z < WMAX; ++z)
+#pragma unroll
+            for (int x = 0; x < 6; ++x) G[z][x] = 0.f;
+        double f0 = 0.0, f1 = 0.0;
+        const double Ii0 = I0b[i], pdi = (I1b[i] - Ii0) / hb;
+        for (int32_t t = 0; t < wt; ++t) {
+            const double2 *P = INC + (7 * t) * 64 + l;
+            const int4 q = *reinterpret_cast<const int4 *>(P);
+            const double aj = I0b[q.z], ak = I0b[q.w], bj = I1b[q.z], bk = I1b[q.w];
+            const double2 g01 = P[1 * 64], g23 = P[2 * 64], g45 = P[3 * 64], g67 = P[4 * 64], g8a = P[5 * 64];
+            const int4 ws = *reinterpret_cast<const int4 *>(P + 6 * 64);
+            const double g[9] = {g01.x, g01.y, g23.x, g23.y, g45.x, g45.y, g67.x, g67.y, g8a.x};
+            asm_inc_term<WMAX>(i, q.x < M, q.y, q.z, q.w, ws.y, g, g8a.y, __int_as_float(ws.x), ei, Ii0, pdi, aj, ak,
+                               bj, bk, hb, f0, f1, G);
+        }
+        const int64_t vi = (int64_t)b * N + i;
+        float eif[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) eif[k] = (float)ei[k];
+#pragma unroll
+        for (int z = 0; z < WMAX; ++z) {
+            if (z < wa) {  // slice-uniform
+                const float4 *S = reinterpret_cast<const float4 *>(SLT + (3 * z) * 64 + l);
+                const float4 s0 = S[0];
+                const int32_t fl = __float_as_int(s0.x);
+                if (fl & 1) {
+                    const float4 s1 = S[64];
+                    const float ej[6] = {s0.y, s0.z, s0.w, s1.x, s1.y, s1.z};
+                    float acc[4];
+                    g3_slot(G[z], eif, ej, acc);
+                    row_slot_store(acc, S[128], z == 0, (fl & 2) != 0, (int64_t)b * sell_nb + o + z * 64 + l, vi, f0,
+                                   f1, block_jacobi, A, dinv32, rhs, Ah);
+                }
+            }
+        }
     }
 }
 
@@ -929,10 +1104,34 @@ void launch_assemble(mof_mesh *m, int32_t B, const double *I0, const double *I1,
         m->N, m->M, nblk_rows, B, snb, m->sell_off.p, m->sell_col.p, m->vptr.p, m->tsell_off.p,                    \
         reinterpret_cast<const int4 *>(m->tinc.p), m->tslot.p, m->w12_32.p, m->a2s32.p, bj, w.A32.p, w.dinv32.p,   \
         w.rhs.p, bf.A0h, m->n_own, mirw, geo)
-    if (rows && W <= 8)
+    if (rows && m->asm_lds) {
+        // the staged kernel (mesh_set_own: max_w <= 8 and the widest slice fits
+        // kAsmLdsCap). A small mesh or batch (fewer than kAsmLdsFill workgroups
+        // at kAsmLdsTrips systems per wave) takes one system per wave instead, so
+        // the launch still fills the CUs; a system's bits do not depend on the split
+        static LdsLimit limit;
+        const auto kern = &k_assemble_lds<kAsmLdsW, kAsmLdsTrips>, kern1 = &k_assemble_lds<kAsmLdsW, 1>;
+        raise_lds_limit(limit, m->device,
+                        {reinterpret_cast<const void *>(kern), reinterpret_cast<const void *>(kern1)}, kAsmLdsCap);
+        MOF_REQUIRE(W <= kAsmLdsMaxW && m->asm_lds_bytes <= kAsmLdsCap, "staged assembly: mesh not eligible");
+        const int32_t nsl = m->pat.nslices;
+        int32_t nchunk = (B + kAsmLdsW * kAsmLdsTrips - 1) / (kAsmLdsW * kAsmLdsTrips);
+        const bool one = (int64_t)nsl * nchunk < kAsmLdsFill && !g_force_assembly_trips.load();
+        if (one) nchunk = (B + kAsmLdsW - 1) / kAsmLdsW;
+        const unsigned grid = xcd_grid(nsl, nchunk, kGrpAsmLds);
+        MOF_REQUIRE((int64_t)grid * 64 * kAsmLdsW < ((int64_t)1 << 32), "launch grid past 2^32 work-items");
+        g_assembly_launches[one ? 1 : 2]++;
+        (one ? kern1 : kern)<<<dim3(grid), 64 * kAsmLdsW, (size_t)m->asm_lds_bytes, s>>>(
+            m->N, m->M, nsl, B, snb, m->sell_off.p, m->sell_col.p, m->vptr.p, m->tsell_off.p,
+            reinterpret_cast<const int4 *>(m->tinc.p), m->tslot.p, m->w12_32.p, m->a2s32.p, bj, w.A32.p, w.dinv32.p,
+            w.rhs.p, bf.A0h, m->n_own, mirw, geo);
+    } else if (rows && W <= 8) {
+        g_assembly_launches[0]++;
         MOF_ASM_RC_LAUNCH(8);
-    else if (rows)
+    } else if (rows) {
+        g_assembly_launches[0]++;
         MOF_ASM_RC_LAUNCH(16);
+    }
 #undef MOF_ASM_RC_LAUNCH
     else if (precision == MOF_PREC_MIXED)
         k_assemble_mixed<<<gb, kWG, 0, s>>>(snb, m->N, m->M, B, m->sell_blk.p, m->blk_row.p, m->vcol.p,

@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <functional>
 #include <future>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -162,6 +163,38 @@ extern std::atomic<int> g_force_residual_rows;
 extern std::atomic<int> g_force_residual_trips;
 // launches so far of k_residual_rcn, the one-trip and the multi-trip k_residual_lds (mof_test_residual_launches)
 extern std::atomic<int64_t> g_residual_launches[3];
+// The staged row assembly (k_assemble_lds, mof_assemble.hip) keeps, of one
+// 64-row slice, what every system reads alike in LDS: per row 112 B per
+// incidence slot (tinc record, 9 hat gradients, A_T, A_T / 12 as float, tslot;
+// seven 16-byte planes), 48 B per a2 slot (flags, e_j as floats, the fp32
+// lambda a2 block; three planes) and 48 B (its own bases). A mesh (or
+// decomposed part) takes the kernel when its widest row fits the 8 register
+// slots of k_assemble_rows_rc<8> and its widest slice fits kAsmLdsCap, the
+// fixed dynamic-LDS limit the kernel is given; the pattern alone decides.
+constexpr int64_t kAsmLdsCap = 160 * 1024;
+constexpr int32_t kAsmLdsMaxW = 8;
+inline int64_t asm_slice_bytes(int32_t w_a2, int32_t w_inc) {
+    return (int64_t)kSlice * ((int64_t)w_inc * 112 + (int64_t)w_a2 * 48 + 48);
+}
+int64_t asm_staged_bytes(const Pattern &pat);  // the maximum over the slices
+inline bool asm_staged_fits(const Pattern &pat) {
+    return pat.max_w <= kAsmLdsMaxW && asm_staged_bytes(pat) <= kAsmLdsCap;
+}
+// tests only (mof_test_force_assembly_rows): every mesh set up from now on keeps k_assemble_rows_rc
+extern std::atomic<int> g_force_assembly_rows;
+// tests only (mof_test_force_assembly_trips): the staged assembly's multi-trip instance whatever the launch's size
+extern std::atomic<int> g_force_assembly_trips;
+// launches so far of k_assemble_rows_rc, the one-trip and the multi-trip k_assemble_lds (mof_test_assembly_launches)
+extern std::atomic<int64_t> g_assembly_launches[3];
+
+// A kernel's dynamic-LDS limit, raised once per process and device to a fixed
+// cap -- never to one mesh's own size, which a later mesh would lower under an
+// earlier mesh's launches or overrun. One LdsLimit (static) per kernel family.
+struct LdsLimit {
+    static constexpr int kMaxDev = 64;
+    std::once_flag once[kMaxDev];
+};
+void raise_lds_limit(LdsLimit &st, int device, std::initializer_list<const void *> kernels, int64_t cap);
 
 // Per-batch device workspace (capacity B systems).
 struct Workspace {
@@ -296,6 +329,9 @@ struct mof_mesh {
     // the re-forming fp64 residual runs staged in LDS (res_staged_bytes <= kResLdsCap)
     int64_t res_lds_bytes = 0;
     bool res_lds = false;
+    // the mixed-precision row assembly runs staged in LDS (asm_staged_fits)
+    int64_t asm_lds_bytes = 0;
+    bool asm_lds = false;
     mof::DevArray<double> e, gw, iw, area, a2;  // a2: [sell_nb][4] (unscaled, bit-exact)
     // operator copies: lambda*a2 (cached per lambda) and A_T/12 with a zero slot M
     mof::DevArray<double> a2s64, w12_64;

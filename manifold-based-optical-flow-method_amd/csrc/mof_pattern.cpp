@@ -278,6 +278,14 @@ int64_t res_staged_bytes(const Pattern &pat) {
     return mx;
 }
 
+int64_t asm_staged_bytes(const Pattern &pat) {
+    int64_t mx = 0;
+    for (int32_t s = 0; s < pat.nslices; ++s)
+        mx = std::max(mx, asm_slice_bytes((pat.sell_off[s + 1] - pat.sell_off[s]) / kSlice,
+                                          (pat.tsell_off[s + 1] - pat.tsell_off[s]) / kSlice));
+    return mx;
+}
+
 // Reverse Cuthill-McKee order of the vertex graph in `pat` (adjacency
 // only). Returns perm with perm[old] = new. BFS from a pseudo-peripheral
 // vertex of every connected component, neighbours in increasing degree,

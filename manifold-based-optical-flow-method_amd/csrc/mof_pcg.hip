@@ -1401,14 +1401,10 @@ MatArgs<V> make_mat(mof_mesh *m, const V *A) {
 // otherwise launch past the limit an earlier one set).
 void launch_residual_lds(mof_mesh *m, const OpArgs<double> &op, int32_t nblk, int32_t B, hipStream_t s, RedArgs rd,
                          const double *rhs, const double *x64, const int32_t *sysi, double *r64, double *part) {
-    constexpr int kMaxDev = 64;
-    static std::once_flag once[kMaxDev];
+    static LdsLimit limit;
     const auto kern = &k_residual_lds<kResNS, kLdsW, kLdsTrips>, kern1 = &k_residual_lds<kResNS, kLdsW, 1>;
-    MOF_REQUIRE(m->device >= 0 && m->device < kMaxDev, "device index out of range");
-    std::call_once(once[m->device], [&] {
-        for (const void *k : {reinterpret_cast<const void *>(kern), reinterpret_cast<const void *>(kern1)})
-            MOF_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kResLdsCap));
-    });
+    raise_lds_limit(limit, m->device, {reinterpret_cast<const void *>(kern), reinterpret_cast<const void *>(kern1)},
+                    kResLdsCap);
     const int32_t nsl = m->pat.nslices, npair = (B + kResNS - 1) / kResNS;
     // a small mesh or batch (fewer than kLdsFill workgroups at kLdsTrips pairs
     // per wave) takes one pair per wave instead, so the launch still fills

@@ -59,7 +59,9 @@ EXPORTS = (
     "mof_singularities_compact", "mof_xcd_map_check", "mof_xcd_batch_cap", "mof_dd_create_rank_host",
     "mof_index_probe", "mof_test_force_index32", "mof_wave_speed", "mof_streamline_map", "mof_streamlines",
     "mof_test_streamline_pass", "mof_residual_probe", "mof_test_force_residual_rows",
-    "mof_test_force_residual_trips", "mof_test_residual_launches",
+    "mof_test_force_residual_trips", "mof_test_residual_launches", "mof_assembly_probe",
+    "mof_test_force_assembly_rows", "mof_test_force_assembly_trips", "mof_test_assembly_launches",
+    "mof_test_assembly_readback",
 )
 
 
@@ -197,6 +199,11 @@ def lib():
             "mof_test_force_residual_rows": ([i32], ctypes.c_int),
             "mof_test_force_residual_trips": ([i32], ctypes.c_int),
             "mof_test_residual_launches": ([P], ctypes.c_int),
+            "mof_assembly_probe": ([P, i32, i32, u32, P, P], ctypes.c_int),
+            "mof_test_force_assembly_rows": ([i32], ctypes.c_int),
+            "mof_test_force_assembly_trips": ([i32], ctypes.c_int),
+            "mof_test_assembly_launches": ([P], ctypes.c_int),
+            "mof_test_assembly_readback": ([P, i32, P, P, P, P], ctypes.c_int),
             "mof_xcd_map_check": ([i32, i32, i32], ctypes.c_int),
             "mof_xcd_batch_cap": ([i64, i32, P], ctypes.c_int),
             "mof_singularities_compact": ([i32, P, P, i32, i32, P, i32, f64, u32, P, i64, P, P, P, P, P,

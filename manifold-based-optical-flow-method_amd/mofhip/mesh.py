@@ -379,3 +379,70 @@ def residual_launches() -> dict:
     c = np.zeros(3, dtype=np.int64)
     L.check(L.lib().mof_test_residual_launches(L.ptr(c)))
     return {"rows": int(c[0]), "staged_one": int(c[1]), "staged_multi": int(c[2])}
+
+
+def assembly_probe(triangles, n_vertices: int, reorder: bool = True) -> dict:
+    """Host-only diagnostic (mof_assembly_probe): ``staged_bytes``, the LDS the
+    staged row assembly (k_assemble_lds) needs for the widest 64-row slice of
+    this triangle list -- 64 (112 incidence slots + 48 a2 slots + 48) bytes --
+    and ``staged_used``, whether a handle of the mesh takes that kernel (no
+    row wider than 8 blocks and the bytes fit the kernel's fixed LDS limit).
+    The batch plays no part."""
+    T = np.ascontiguousarray(triangles, dtype=np.int32)
+    flags = 0 if reorder else L.MOF_NO_REORDER
+    nb, used = ctypes.c_int64(0), ctypes.c_int32(0)
+    L.check(L.lib().mof_assembly_probe(L.ptr(T), int(n_vertices), len(T), flags, ctypes.byref(nb),
+                                       ctypes.byref(used)))
+    return {"staged_bytes": int(nb.value), "staged_used": bool(used.value)}
+
+
+class force_assembly_rows:
+    """Tests only (mof_test_force_assembly_rows): handles created inside the
+    block keep the row kernel k_assemble_rows_rc where the staged one would fit."""
+
+    def __enter__(self):
+        L.check(L.lib().mof_test_force_assembly_rows(1))
+        return self
+
+    def __exit__(self, *exc):
+        L.check(L.lib().mof_test_force_assembly_rows(0))
+        return False
+
+
+class force_assembly_trips:
+    """Tests only (mof_test_force_assembly_trips): every staged assembly launch
+    inside the block takes the multi-trip kernel of the large launches."""
+
+    def __enter__(self):
+        L.check(L.lib().mof_test_force_assembly_trips(1))
+        return self
+
+    def __exit__(self, *exc):
+        L.check(L.lib().mof_test_force_assembly_trips(0))
+        return False
+
+
+def assembly_launches() -> dict:
+    """Tests only (mof_test_assembly_launches): launches so far in this process
+    of the row assembly kernel (``rows``) and of the staged kernel with one
+    (``staged_one``) and several (``staged_multi``) trips per wave."""
+    c = np.zeros(3, dtype=np.int64)
+    L.check(L.lib().mof_test_assembly_launches(L.ptr(c)))
+    return {"rows": int(c[0]), "staged_one": int(c[1]), "staged_multi": int(c[2])}
+
+
+def assembly_readback(mesh: "DeviceMesh", system: int, device=None) -> dict:
+    """Tests only (mof_test_assembly_readback): what the handle's last
+    mixed-precision assembly left for its system ``system``, in the internal
+    order -- ``A32`` (sell_blocks, 4) float32, ``A0h`` (sell_blocks,) uint64
+    (the multigrid's bf16 blocks; None without multigrid storage) and ``rhs``
+    (N, 2) float64. Positions the assembly never writes are not initialised."""
+    nb = int(mesh.info(device)["sell_blocks"])
+    A32 = np.zeros((nb, 4), dtype=np.float32)
+    A0h = np.zeros(nb, dtype=np.uint64)
+    rhs = np.zeros((mesh.N, 2), dtype=np.float64)
+    have = ctypes.c_int32(0)
+    with mesh.lock(device):
+        L.check(L.lib().mof_test_assembly_readback(mesh.handle(device), int(system), L.ptr(A32), L.ptr(A0h),
+                                                   L.ptr(rhs), ctypes.byref(have)))
+    return {"A32": A32, "A0h": A0h if have.value else None, "rhs": rhs}
