@@ -588,6 +588,74 @@ int mof_dd_solve_range(mof_dd *dd, const double *I, const double *I2, const doub
                        int32_t T, int32_t k0, int32_t k1, double lambda, const mof_opts *opts,
                        double *V_out, mof_stats *stats);
 
+/* ---- Winding numbers on the mesh: the reference's S7_winding_line.py --------
+ * For a centre vertex c with e1, e2 = e_c and n = e1 x e2 (S7:120-165):
+ *   ring l (l = 0 .. max_level - 1): the vertices at edge distance exactly
+ *     l + 1 from c, in polar order: keys atan2(v, u) ascending, (u, v) =
+ *     (proj . e1, proj . e2), proj = w - (w . n) n / (n . n), w = p_j - p_c
+ *     (formed in float32 on a MOF_GEOM_F32_POINTS handle, everything after it
+ *     in fp64); equal keys go to the smaller vertex id of the caller's order
+ *     (the reference's stable sort keeps VTK's ring order there, which is no
+ *     property of the mesh). Boundary rings are open arcs and are still
+ *     walked as closed polygons, as the reference walks them;
+ *   winding number of a ring: per ring vertex Vt = V_j - (V_j . n) n / (n . n),
+ *     (a, b) = (Vt . e1 / e1 . e1, Vt . e2 / e2 . e2); the signed angles
+ *     between consecutive unit vectors of the sorted cyclic sequence (arccos
+ *     of the dot clamped to [-1, 1], negated when the 2-D cross product is
+ *     < 0), summed in sequence order and divided by 2 pi. A zero or NaN
+ *     vector gives NaN, which fails every check;
+ *   count and type: level 0 sets type = -1 for -1.01 <= wn <= -0.99, +1 for
+ *     0.99 <= wn <= 1.01 (count = 1), else 0 -- and does not stop: level 1 is
+ *     still evaluated, fails and stops. A level >= 1 within +-[0.999, 1.001]
+ *     of the type adds one to the count, any other stops. An empty ring (the
+ *     mesh is exhausted: a 642-vertex sphere after 20-24 rings) stops like a
+ *     failed check where the reference raises IndexError.
+ * The sums are taken in ring order without floating-point atomics: results do
+ * not depend on the handle's internal vertex order. */
+#define MOF_WIND_ALL_LEVELS 1024u /* mof_winding_levels: evaluate every
+                                      non-empty level whatever the checks say
+                                      (wn over scale); count and type unchanged */
+
+/* The sorted ring table of C centres (host pointers, caller's ids):
+ * ring l of centre q is ring_vtx[level_off[q * (max_level + 1) + l] ..
+ * level_off[q * (max_level + 1) + l + 1]); *total (always written) = entries.
+ * When total > cap nothing else is written and MOF_E_ARG is returned: call
+ * again with cap >= *total. Ring membership is a breadth-first search on the
+ * host (threads: MOF_IO_THREADS, else OMP_NUM_THREADS, else 4); keys and sort run on
+ * the device, one workgroup per ring of any size. */
+int mof_winding_rings(mof_mesh *mesh, const int32_t *centres, int32_t C, int32_t max_level, int64_t cap,
+                      int64_t *total, int64_t *level_off, int32_t *ring_vtx);
+/* Q queries (frame[q], centre[q]) into V_coord (K, N, 3): wn (Q, max_level)
+ * per level (NaN: not evaluated), count (Q) and type (Q; +1 / -1 / 0). Any
+ * output may be NULL, not all. The centres are deduplicated and their ring
+ * table built once; one wave evaluates one query. Queries may repeat, be
+ * unsorted and share centres across frames. Host pointers, or with
+ * MOF_IO_DEVICE device pointers throughout (flags: MOF_WIND_ALL_LEVELS). */
+int mof_winding_levels(mof_mesh *mesh, const double *V_coord, int32_t K, const int32_t *frame,
+                       const int32_t *centre, int32_t Q, int32_t max_level, uint32_t flags, void *stream, double *wn,
+                       int32_t *count, int8_t *type);
+/* Level 0 at every vertex of every field: wn0 (K, N) and index (K, N; the
+ * level-0 type, 0 where wn0 is NaN), either may be NULL. wn0[k, c] equals
+ * mof_winding_levels' wn[., 0] for (k, c) bit for bit. Reads the neighbours of
+ * each vertex in polar order from a table built on the handle at the first
+ * call; the fields go through in passes of bounded size. */
+int mof_winding_map(mof_mesh *mesh, const double *V_coord, int32_t K, uint32_t flags, void *stream, double *wn0,
+                    int8_t *index);
+/* Test hook: fields per pass of mof_winding_map, 0 = the library's choice. */
+int mof_test_winding_pass(int32_t fields);
+/* Measurement helper (bench_winding.py): milliseconds the last
+ * mof_winding_levels / mof_winding_rings call of this process spent in the
+ * host search, the sort kernel and the evaluation kernel (ms[0..2]). */
+int mof_winding_timing(double *ms);
+/* surf.find_closest_point restated: vertex[q] = the vertex minimising
+ * (dx dx + dy dy) + dz dz in fp64 without contraction, the lowest id of the
+ * caller's order on ties (points (Q, 3) fp64; host pointers, or device
+ * pointers with MOF_IO_DEVICE). VTK's point locator is not restated: parity
+ * with pyvista at exactly equidistant points is unpinned, as for
+ * mof_point_normals. */
+int mof_closest_vertices(mof_mesh *mesh, const double *points, int32_t Q, uint32_t flags, void *stream,
+                         int32_t *vertex);
+
 /* Measurement helper for bench.py: launches the PCG SpMV kernel `reps` times
  * back to back on `batch` systems of the last solve's working set, timed with
  * HIP events on the handle's stream. Returns the mean launch time and the

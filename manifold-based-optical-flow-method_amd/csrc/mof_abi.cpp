@@ -763,6 +763,8 @@ int mof_mesh_destroy(mof_mesh *m) {
             m->wave = nullptr;
             mof::stream_destroy(m->sline);
             m->sline = nullptr;
+            mof::wind_destroy(m->wind);
+            m->wind = nullptr;
             if (m->stream) (void)hipStreamDestroy(m->stream);
             m->stream = nullptr;
             delete m;  // DevArray destructors free on the current (guarded) device

@@ -255,6 +255,7 @@ struct AmgHierarchy;  // mof_amg.h
 class HostStage;      // mof_hostio.h
 struct WaveState;     // mof_wave.hip
 struct StreamState;   // mof_streamline.hip
+struct WindState;     // mof_winding.hip
 
 // Host state of one mesh shared by its handles on several devices
 // (mof_mesh_create builds it once, mof_mesh_clone reuses it): the inputs in
@@ -368,6 +369,9 @@ struct mof_mesh {
     // mof_streamline_map / mof_streamlines: the per-slot direction table and
     // the pass workspace, built on first use (mof_streamline.hip)
     mof::StreamState *sline = nullptr;
+    // mof_winding_*: the geometry, the polar-ordered neighbour table and the
+    // ring-table / pass workspace, built on first use (mof_winding.hip)
+    mof::WindState *wind = nullptr;
 };
 
 namespace mof {
@@ -420,6 +424,14 @@ bool stream_lists(mof_mesh *m, const double *V, int32_t K, int32_t min_len, bool
 void stream_destroy(StreamState *st);
 // tests only (mof_test_streamline_pass): fields per pass of the two calls above, 0 = the library's choice
 extern std::atomic<int> g_stream_pass_fields;
+
+// mof_winding_* (mof_winding.hip, mof_winding_host.cpp)
+void wind_destroy(WindState *st);
+// Rings of C centres (internal ids) over the pattern's adjacency by breadth-
+// first search on host threads: off (C * (L + 1)) and the members (internal
+// ids, each ring in search order); an exhausted centre's later rings are empty.
+void wind_bfs(const Pattern &pat, const int32_t *centres, int32_t C, int32_t L, std::vector<int64_t> &off,
+              std::vector<int32_t> &vtx);
 
 // Timed SpMV launches: each is charged with the systems it actually
 // processed (a system that converged, or failed, earlier in a chunk of

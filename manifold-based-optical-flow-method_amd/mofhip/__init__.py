@@ -15,3 +15,5 @@ from .wave import (wave_speed, wave_velocity_phase, wave_velocity_amplitude,  # 
                    compute_temporal_gradient_phase)
 from .streamline import (streamline_map, streamline_map_device, streamline_lists,  # noqa: F401
                          track_static_vectorfields_over_time, extract_static_streamline_dot_product)
+from .winding import (winding_map, winding_map_device, winding_levels, winding_levels_device,  # noqa: F401
+                      winding_rings, closest_vertices, calculate_winding_numbers, winding_lines)

@@ -43,6 +43,7 @@ MOF_CSV_ROUND_TRIP = 1
 MOF_COORDS_F32 = 32
 MOF_DD_STAGED = 64
 MOF_WAVE_PHASE = 512
+MOF_WIND_ALL_LEVELS = 1024
 MOF_CSR_A2 = 0
 MOF_CSR_A_LAST = 1
 
@@ -61,7 +62,8 @@ EXPORTS = (
     "mof_test_streamline_pass", "mof_residual_probe", "mof_test_force_residual_rows",
     "mof_test_force_residual_trips", "mof_test_residual_launches", "mof_assembly_probe",
     "mof_test_force_assembly_rows", "mof_test_force_assembly_trips", "mof_test_assembly_launches",
-    "mof_test_assembly_readback",
+    "mof_test_assembly_readback", "mof_winding_rings", "mof_winding_levels", "mof_winding_map",
+    "mof_test_winding_pass", "mof_winding_timing", "mof_closest_vertices",
 )
 
 
@@ -190,6 +192,12 @@ def lib():
             "mof_streamline_map": ([P, P, i32, u32, P, P, P], ctypes.c_int),
             "mof_streamlines": ([P, P, i32, i32, u32, P, i64, i64, P, P, P, P], ctypes.c_int),
             "mof_test_streamline_pass": ([i32], ctypes.c_int),
+            "mof_winding_rings": ([P, P, i32, i32, i64, P, P, P], ctypes.c_int),
+            "mof_winding_levels": ([P, P, i32, P, P, i32, i32, u32, P, P, P, P], ctypes.c_int),
+            "mof_winding_map": ([P, P, i32, u32, P, P, P], ctypes.c_int),
+            "mof_test_winding_pass": ([i32], ctypes.c_int),
+            "mof_winding_timing": ([P], ctypes.c_int),
+            "mof_closest_vertices": ([P, P, i32, u32, P, P], ctypes.c_int),
             "mof_singularities": ([i32, P, P, i32, i32, P, i32, f64, u32, P, P, P, P, P],
                                   ctypes.c_int),
             "mof_amg_probe": ([P, P, i32, i32, P, P, P, P], ctypes.c_int),
