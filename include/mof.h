@@ -483,6 +483,60 @@ int mof_test_assembly_launches(int64_t *counts);
 int mof_test_assembly_readback(mof_mesh *mesh, int32_t system, float *A32, void *A0h, double *rhs,
                                int32_t *have_A0h);
 
+/* Test hook (no device launch): the host multigrid hierarchy this handle's
+ * preconditioner was built from (after its first multigrid solve or
+ * mof_mesh_prepare), one level per call. *n_levels receives the level count;
+ * level < 0 returns it (and omegas) alone. Every array is optional: call once
+ * with them NULL for sizes[0..16) =
+ *   0 n (nodes)   1 bs (2 on level 0, 3 below)   2 sell_nb (SELL positions)
+ *   3 entries of sell_off   4 smoothed (the prolongator to the next level)
+ *   5 entries of agg   6 of pptr   7 of pcol   8 of Q (floats)   9 of gptr
+ *   10 of gent (ints; 3 per gather term)   11 regular (the handle's bf16
+ *   iterates and level-0 slab)   12 the handle's row kernels read level 0
+ *   symmetrically   13 nc (coarsest dofs)   14 cap (systems of
+ *   multigrid storage)   15 the level keeps an int8 sweep copy (Ah).
+ * omegas[0..2) = the fine and the coarse smoother damping.
+ * sell_off, sell_col, sell_row, diag_pos (n): the level's SELL-64 layout; a
+ * padding position has sell_row >= n, or sell_col == sell_row away from
+ * diag_pos. Level 0's are the mesh's own, with mirror (sell_nb) the table the
+ * level-0 gather lists were built with (every lower block read as its upper
+ * twin transposed, whichever way the row kernels read): the position to read,
+ * | 1 << 30 if transposed, -1 for padding. Levels >= 1: dead (3 n: dofs whose diagonal
+ * carries + 1) and twin (sell_nb: an upper block's lower twin, -1 elsewhere).
+ * The transition to the next level (sizes 5..10 are 0 on the coarsest):
+ * agg (n), the prolongator's block rows pptr (n + 1) / pcol as CSR over the
+ * fine nodes with block k's bs x 3 floats at Q[k * bs * 3] (a tentative level
+ * has pptr = 0..n, pcol = agg), and the Galerkin gather lists gptr (next
+ * level's sell_nb + 1) / gent: per term {fine SELL position (level 0: a mirror
+ * entry; < 0: a decomposed part's ghost block), P block of the row, P block of
+ * the column}. */
+int mof_test_amg_levels(mof_mesh *mesh, int32_t level, int32_t *n_levels, int64_t *sizes, float *omegas,
+                        int32_t *sell_off, int32_t *sell_col, int32_t *sell_row, int32_t *diag_pos, uint8_t *dead,
+                        int32_t *twin, int32_t *mirror, int32_t *agg, int32_t *pptr, int32_t *pcol, float *Q,
+                        int32_t *gptr, int32_t *gent);
+/* Test hook: a plain device-to-host copy, after a stream synchronize, of what
+ * the handle's last multigrid setup left for its system `system` on level
+ * `level` >= 1: A (12 floats per SELL position: 3 rows padded to 4), the
+ * block-Jacobi inverse Dh (4 words per node: bf16 entries 0..7) and Dh22 (one
+ * bf16 per node: entry 8), the int8 sweep copy Ah (2 words per position: codes
+ * 0..7, offset binary) and Ah22 (2 half-words per position: code 8, then the
+ * block's bf16 scale) where sizes[15] of mof_test_amg_levels says so, and on
+ * the coarsest level cinv (nc x nc floats, row-major). Any output may be
+ * NULL. An error without a built multigrid or for a system >= cap. */
+int mof_test_amg_readback(mof_mesh *mesh, int32_t level, int32_t system, float *A, uint32_t *Dh, uint16_t *Dh22,
+                          uint32_t *Ah, uint16_t *Ah22, float *cinv);
+/* Test hook (never read from the environment): while on, every multigrid
+ * setup takes the per-position Galerkin products (k_galerkin0_ns,
+ * k_galerkin3_ns) that otherwise only run where a by-entry grid would pass
+ * 2^32 work-items -- their results are compared with the by-entry kernels' bit
+ * for bit. A smoothed level 0's products by system slab stay (0: back to the
+ * default). */
+int mof_test_force_galerkin_ns(int32_t on);
+/* Test hook: counts[0..8) = launches so far in this process of k_galerkin0_ns,
+ * k_galerkin0_ent, k_galerkin_sys<2> from the fp32 and from the bf16 slab,
+ * k_galerkin_sys<3>, k_galerkin3_ns, k_galerkin3_ent and k_galerkin3_big. */
+int mof_test_galerkin_launches(int64_t *counts);
+
 /* Diagnostic (host only): checks that the XCD-aware workgroup order of the
  * row kernels -- nblk row blocks x batch systems, walked in groups of
  * `group` systems (0: all) -- visits every (row block, system) pair exactly

@@ -41,9 +41,9 @@ struct AmgParams {
     // storage formats: 8 / 8).
     int32_t smooth1 = 0;
     const double *a2 = nullptr;  // [sell_nb][4] level-0 a2 in the fine SELL layout (smoothing)
-    // the fine level's mirror table when its operators are read symmetrically
-    // (sell_mirror): level-0 gather entries of lower blocks then point at the
-    // transposed upper block (| kMirT), which is all the assembly writes
+    // the fine level's symmetric mirror table (sell_mirror): level-0 gather
+    // entries of lower blocks point at the transposed upper block (| kMirT),
+    // which is all the assembly writes under symmetric reads
     const int32_t *mirror = nullptr;
     // level-0 aggregation visit order (internal node ids), or null: node
     // order. A mesh renumbered within windows (mesh_prepare_host) passes its
@@ -99,6 +99,9 @@ struct AmgHierarchy {
     std::vector<double> curl;
     double max_curl = 0.0;
     bool folded = false;  // amg_build's auto choice rebuilt it with level 1 smoothed
+    // the fine level's mirror table the level-0 gather lists were built with
+    // (amg_build: sell_mirror with symmetric reads, whichever way the row kernels read)
+    std::vector<int32_t> mirror;
 };
 
 // the fold criterion on AmgHierarchy::max_curl (amg_build): F3 0.46-0.51, the
@@ -170,6 +173,9 @@ struct AmgDevice {
     // regular meshes) (k_a_slab -> k_galerkin_sys<2>), reused slab by slab
     DevArray<float> aslab;
     bool bf16_fresh = false;  // A0h written by the batch's assembly
+    // the host hierarchy the levels above were uploaded from (amg_build;
+    // mof_test_amg_levels exports it)
+    std::shared_ptr<const AmgHierarchy> H;
 };
 
 }  // namespace mof

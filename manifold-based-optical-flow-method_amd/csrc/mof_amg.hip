@@ -36,7 +36,17 @@
 #include "mof_amg.h"
 #include "mof_rowkern.h"
 
+int mof_io_guard(const std::function<void()> &f);  // mof_abi.cpp: status + mof_last_error
+
 namespace mof {
+
+// tests only (mof_test_force_galerkin_ns): amg_setup_batch takes the
+// per-position products where the by-entry ones would fit
+std::atomic<int> g_force_galerkin_ns{0};
+// launches so far (mof_test_galerkin_launches), in this order
+enum GalKernel { kGal0Ns, kGal0Ent, kGalSys2F32, kGalSys2Bf16, kGalSys3, kGal3Ns, kGal3Ent, kGal3Big, kGalKernels };
+std::atomic<int64_t> g_galerkin_launches[kGalKernels];
+
 namespace {
 
 constexpr int kB3 = 12;  // floats per coarse 3x3 block / per coarse D^-1
@@ -122,6 +132,18 @@ __device__ void inv3(const float (&a)[3][3], float (&o)[3][3]) {
     o[2][0] = (float)(c02 * id);
     o[2][1] = (float)((a01 * a20 - a00 * a21) * id);
     o[2][2] = (float)((a00 * a11 - a01 * a10) * id);
+}
+
+// A product's diagonal block: its entries (r, c) and (c, r) are the same sum
+// folded in two orders; the upper one is kept for both, so the coarse
+// operator is symmetric to the bit inside its diagonal blocks too, as
+// st_pair makes it across the twins (k_coarse_inverse's sweep takes row k
+// for column k: on a matrix symmetric only to rounding its result is off by
+// about cond x asymmetry)
+__device__ __forceinline__ void sym3(float (&a)[3][3]) {
+    a[1][0] = a[0][1];
+    a[2][0] = a[0][2];
+    a[2][1] = a[1][2];
 }
 
 __device__ __forceinline__ void st3(float *A, int64_t idx, const float (&a)[3][3]) {
@@ -301,6 +323,7 @@ __global__ __launch_bounds__(kWG) void k_galerkin0_ns(
 #pragma unroll
             for (int d = 0; d < 3; ++d)
                 if (c_dead[3 * (int64_t)I + d]) Cm[t][d][d] += 1.f;
+            sym3(Cm[t]);
             float D[3][3];
             inv3(Cm[t], D);
             st_h9(Dh, Dh22, (int64_t)b * nC + I, D);
@@ -404,6 +427,7 @@ __global__ __launch_bounds__(kWG) void k_galerkin0_ent(
 #pragma unroll
             for (int d = 0; d < 3; ++d)
                 if (c_dead[3 * (int64_t)I + d]) Cm[d][d] += 1.f;
+            sym3(Cm);
             float D[3][3];
             inv3(Cm, D);
             st_h9(Dh, Dh22, (int64_t)b * nC + I, D);
@@ -553,6 +577,7 @@ __global__ __launch_bounds__(kWG) void k_galerkin_sys(
 #pragma unroll
         for (int d = 0; d < 3; ++d)
             if (c_dead[3 * (int64_t)I + d]) Cm[d][d] += 1.f;
+        sym3(Cm);
         float D[3][3];
         inv3(Cm, D);
         st_h9(Dh, Dh22, (int64_t)b * nC + I, D);
@@ -647,6 +672,7 @@ __global__ __launch_bounds__(kWG) void k_galerkin3_ns(
 #pragma unroll
             for (int d = 0; d < 3; ++d)
                 if (c_dead[3 * (int64_t)I + d]) Cm[t][d][d] += 1.f;
+            sym3(Cm[t]);
             float D[3][3];
             inv3(Cm[t], D);
             st_h9(Dh, Dh22, (int64_t)b * nC + I, D);
@@ -744,6 +770,7 @@ __global__ __launch_bounds__(kWG) void k_galerkin3_ent(
 #pragma unroll
             for (int d = 0; d < 3; ++d)
                 if (c_dead[3 * (int64_t)I + d]) Cm[d][d] += 1.f;
+            sym3(Cm);
             float D[3][3];
             inv3(Cm, D);
             st_h9(Dh, Dh22, (int64_t)b * nC + I, D);
@@ -858,6 +885,7 @@ __global__ __launch_bounds__(kWG) void k_galerkin3_big(
 #pragma unroll
         for (int d = 0; d < 3; ++d)
             if (c_dead[3 * (int64_t)I + d]) Cm[d][d] += 1.f;
+        sym3(Cm);
         float D[3][3];
         inv3(Cm, D);
         st_h9(Dh, Dh22, (int64_t)b * nC + I, D);
@@ -1935,11 +1963,14 @@ bool amg_build(mof_mesh *m) {
             prm.a2 = a2.data();
         }
         if (!m->agg_order.empty()) prm.order = m->agg_order.data();
-        std::vector<int32_t> mir;
-        if (m->sym_reads) {
-            mir = sell_mirror(m->pat, m->n_own, 1, nullptr);
-            prm.mirror = mir.data();
-        }
+        // the level-0 gather lists read every lower block as its upper twin
+        // transposed, whichever way the row kernels read: with plain reads the
+        // fp32 operator's lower blocks are assembled on their own and differ
+        // from the transposed upper ones by rounding, and the products (which
+        // compute the upper coarse blocks and mirror them, st_pair) would
+        // otherwise give the Galerkin operator of no single matrix
+        const std::vector<int32_t> mir = sell_mirror(m->pat, m->n_own, 1, nullptr);
+        prm.mirror = mir.data();
         auto built = std::make_shared<AmgHierarchy>();
         AmgParams p1 = prm;
         // level 1 smoothed at once where level 0 is (irregular or open
@@ -1983,6 +2014,7 @@ bool amg_build(mof_mesh *m) {
             again->folded = true;
             built = again;
         }
+        built->mirror = mir;
         Hp = built;
         if (sh) {
             std::lock_guard<std::mutex> lk(sh->mu);
@@ -1991,6 +2023,7 @@ bool amg_build(mof_mesh *m) {
     }
     if (build_lock.owns_lock()) build_lock.unlock();
     const AmgHierarchy &H = *Hp;
+    G.H = Hp;
     G.omega = prm.omega;
     G.omega1 = prm.omega1;
     // level 0's corrected iterate x0 + Q y: bf16 in place on meshes with the
@@ -2352,7 +2385,8 @@ void amg_setup_batch(mof_mesh *m, int32_t B, hipStream_t s) {
         return 8 * G * ((nq + G - 1) / G) * ((nblk + 7) / 8) * kWG < ((int64_t)1 << 32);
     };
     auto ent_fits = [&](const AmgDevLevel &F) {
-        return (F.nggrp > 0 || F.nbig > 0) && fits(F.nggrp, kGalENS) && fits(F.nbig, kGalBigNS);
+        return !g_force_galerkin_ns.load() && (F.nggrp > 0 || F.nbig > 0) && fits(F.nggrp, kGalENS) &&
+               fits(F.nbig, kGalBigNS);
     };
     // a smoothed level 0: its product, and level 1's when level 1 kept a
     // slab copy, by system slab (k_a_slab -> k_galerkin_sys<2> -> <3>)
@@ -2373,6 +2407,7 @@ void amg_setup_batch(mof_mesh *m, int32_t B, hipStream_t s) {
                                                     reinterpret_cast<const float4 *>(w.A32.p),
                                                     reinterpret_cast<float4 *>(G.aslab.p));
             auto *cs = l1 ? reinterpret_cast<float4 *>(C.slab.p) : nullptr;
+            ++g_galerkin_launches[G.regular ? kGalSys2Bf16 : kGalSys2F32];
             if (G.regular)
                 k_galerkin_sys<2, true><<<sys_grid(C.sell_nb), kWG, 0, s>>>(
                     C.sell_nb, C.n, B, b0, C.sell_row.p, C.diag_pos.p, C.dead.p, C.twin.p, F.gptr.p, F.gent.p, F.Q.p,
@@ -2383,6 +2418,7 @@ void amg_setup_batch(mof_mesh *m, int32_t B, hipStream_t s) {
                     reinterpret_cast<const float4 *>(G.aslab.p), C.A.p, dh(C), C.Dh22.p, ah(C), ah22(C), cs);
             if (l1) {
                 AmgDevLevel &C2 = G.lv[2];
+                ++g_galerkin_launches[kGalSys3];
                 k_galerkin_sys<3><<<sys_grid(C2.sell_nb), kWG, 0, s>>>(
                     C2.sell_nb, C2.n, B, b0, C2.sell_row.p, C2.diag_pos.p, C2.dead.p, C2.twin.p, C.gptr.p, C.gent.p, C.Q.p,
                     reinterpret_cast<const float4 *>(C.slab.p), C2.A.p, dh(C2), C2.Dh22.p, ah(C2), ah22(C2), nullptr);
@@ -2393,6 +2429,15 @@ void amg_setup_batch(mof_mesh *m, int32_t B, hipStream_t s) {
     for (size_t l = l_first; l + 1 < L; ++l) {
         AmgDevLevel &F = G.lv[l], &C = G.lv[l + 1];
         const bool ent = ent_fits(F);
+        // the launch counters of the branches below (mof_test_galerkin_launches)
+        if (l == 0) {
+            ++g_galerkin_launches[ent ? kGal0Ent : kGal0Ns];
+        } else if (ent) {
+            if (F.nggrp > 0) ++g_galerkin_launches[kGal3Ent];
+            if (F.nbig > 0) ++g_galerkin_launches[kGal3Big];
+        } else {
+            ++g_galerkin_launches[kGal3Ns];
+        }
         if (l == 0 && ent)
             k_galerkin0_ent<<<dim3(xcd_grid(F.nggrp, (B + kGalENS - 1) / kGalENS, kGrpGal)), kWG, 0, s>>>(
                 F.nggrp, F.ggrp.p, C.n, B, C.sell_row.p, C.diag_pos.p, C.dead.p, C.twin.p, F.gptr.p, F.gent.p, F.Q.p,
@@ -2581,4 +2626,141 @@ float amg_set_omega(mof_mesh *m, float omega) {
 
 int32_t amg_levels(const mof_mesh *m) { return m->amg && m->amg->built ? (int32_t)m->amg->lv.size() : 0; }
 
+namespace {
+struct DeviceGuard {
+    int prev = 0;
+    explicit DeviceGuard(int d) {
+        (void)hipGetDevice(&prev);
+        MOF_HIP(hipSetDevice(d));
+    }
+    ~DeviceGuard() { (void)hipSetDevice(prev); }
+};
+}  // namespace
+
 }  // namespace mof
+
+// ---- test hooks (include/mof.h) ------------------------------------------------
+
+extern "C" {
+
+int mof_test_amg_levels(mof_mesh *m, int32_t level, int32_t *n_levels, int64_t *sizes, float *omegas,
+                        int32_t *sell_off, int32_t *sell_col, int32_t *sell_row, int32_t *diag_pos, uint8_t *dead,
+                        int32_t *twin, int32_t *mirror, int32_t *agg, int32_t *pptr, int32_t *pcol, float *Q,
+                        int32_t *gptr, int32_t *gent) {
+    return mof_io_guard([&] {
+        MOF_REQUIRE(m && n_levels, "NULL argument");
+        mof::mesh_join_prep(m);
+        const mof::AmgDevice *G = m->amg;
+        MOF_REQUIRE(G && G->built && G->H && G->lv.size() >= 2 && G->H->levels.size() == G->lv.size(),
+                    "the handle has no built multigrid");
+        const mof::AmgHierarchy &H = *G->H;
+        *n_levels = (int32_t)H.levels.size();
+        if (omegas) {
+            omegas[0] = G->omega;
+            omegas[1] = G->omega1;
+        }
+        if (level < 0) return;  // the level count alone
+        MOF_REQUIRE(level < *n_levels, "no such level");
+        const mof::AmgLevel &L = H.levels[level];
+        // level 0: the mesh's own SELL layout (the hierarchy's level 0 only
+        // carries the adjacency) and the mirror table on the device
+        const std::vector<int32_t> &off = level == 0 ? m->pat.sell_off : L.sell_off;
+        const std::vector<int32_t> &col = level == 0 ? m->pat.sell_col : L.sell_col;
+        const std::vector<int32_t> &dpos = level == 0 ? m->pat.diag_pos : L.diag_pos;
+        const int64_t nb = off.empty() ? 0 : off.back();
+        MOF_REQUIRE(nb == G->lv[level].sell_nb && L.n == G->lv[level].n, "host and device levels disagree");
+        if (sizes) {
+            const int64_t v[16] = {L.n,
+                                   L.bs,
+                                   nb,
+                                   (int64_t)off.size(),
+                                   L.smoothed,
+                                   (int64_t)L.agg.size(),
+                                   (int64_t)L.pptr.size(),
+                                   (int64_t)L.pcol.size(),
+                                   (int64_t)L.Q.size(),
+                                   (int64_t)L.gptr.size(),
+                                   (int64_t)L.gent.size(),
+                                   G->regular,
+                                   level == 0 && m->sym_reads,
+                                   G->nc,
+                                   G->cap,
+                                   G->lv[level].Ah.n > 1};
+            std::copy(v, v + 16, sizes);
+        }
+        auto put = [](auto *dst, const auto &src) {
+            if (dst) std::copy(src.begin(), src.end(), dst);
+        };
+        put(sell_off, off);
+        put(sell_col, col);
+        put(diag_pos, dpos);
+        if (sell_row) {
+            if (level == 0)
+                for (size_t s = 0; s + 1 < off.size(); ++s)
+                    for (int64_t q = off[s]; q < off[s + 1]; ++q)
+                        sell_row[q] = (int32_t)(s * mof::kSlice + (q - off[s]) % mof::kSlice);
+            else
+                put(sell_row, L.sell_row);
+        }
+        if (level > 0) {
+            put(dead, L.dead);
+            if (twin) {  // as amg_build uploads it: each upper block's lower twin, -1 elsewhere
+                std::fill(twin, twin + nb, -1);
+                for (size_t k = 0; k < L.low.size(); ++k) twin[L.twin[k]] = L.low[k];
+            }
+        } else if (mirror) {
+            MOF_REQUIRE((int64_t)H.mirror.size() == nb, "the hierarchy keeps no level-0 mirror table");
+            put(mirror, H.mirror);
+        }
+        put(agg, L.agg);
+        put(pptr, L.pptr);
+        put(pcol, L.pcol);
+        put(Q, L.Q);
+        put(gptr, L.gptr);
+        put(gent, L.gent);
+    });
+}
+
+int mof_test_amg_readback(mof_mesh *m, int32_t level, int32_t system, float *A, uint32_t *Dh, uint16_t *Dh22,
+                          uint32_t *Ah, uint16_t *Ah22, float *cinv) {
+    return mof_io_guard([&] {
+        MOF_REQUIRE(m, "mesh is NULL");
+        mof::mesh_join_prep(m);
+        mof::AmgDevice *G = m->amg;
+        MOF_REQUIRE(G && G->built && G->lv.size() >= 2, "the handle has no built multigrid");
+        MOF_REQUIRE(level >= 1 && level < (int32_t)G->lv.size(), "no such coarse level");
+        MOF_REQUIRE(system >= 0 && system < G->cap, "no multigrid storage for that system");
+        mof::AmgDevLevel &D = G->lv[level];
+        const bool sweep = D.Ah.n > 1, last = level + 1 == (int32_t)G->lv.size();
+        MOF_REQUIRE(sweep || !(Ah || Ah22), "that level keeps no sweep copy");
+        MOF_REQUIRE(last || !cinv, "cinv belongs to the coarsest level");
+        mof::DeviceGuard dg(m->device);
+        MOF_HIP(hipStreamSynchronize(m->stream));
+        const size_t b = (size_t)system, nb = (size_t)D.sell_nb, n = (size_t)D.n, nc = (size_t)G->nc;
+        auto get = [&](auto *dst, const auto &src, size_t per) {
+            if (!dst) return;
+            MOF_REQUIRE(src.n >= per * (b + 1), "multigrid storage smaller than its capacity");
+            MOF_HIP(hipMemcpy(dst, src.p + per * b, per * sizeof(*dst), hipMemcpyDeviceToHost));
+        };
+        get(A, D.A, mof::kB3 * nb);
+        get(Dh, D.Dh, 4 * n);
+        get(Dh22, D.Dh22, n);
+        get(Ah, D.Ah, mof::kAhWords * nb);
+        get(Ah22, D.Ah22, mof::kAh22Words * nb);
+        get(cinv, G->cinv, nc * nc);
+    });
+}
+
+int mof_test_force_galerkin_ns(int32_t on) {
+    mof::g_force_galerkin_ns.store(on != 0);
+    return MOF_OK;
+}
+
+int mof_test_galerkin_launches(int64_t *counts) {
+    return mof_io_guard([&] {
+        MOF_REQUIRE(counts, "NULL argument");
+        for (int k = 0; k < mof::kGalKernels; ++k) counts[k] = mof::g_galerkin_launches[k].load();
+    });
+}
+
+}  // extern "C"

@@ -446,3 +446,88 @@ def assembly_readback(mesh: "DeviceMesh", system: int, device=None) -> dict:
         L.check(L.lib().mof_test_assembly_readback(mesh.handle(device), int(system), L.ptr(A32), L.ptr(A0h),
                                                    L.ptr(rhs), ctypes.byref(have)))
     return {"A32": A32, "A0h": A0h if have.value else None, "rhs": rhs}
+
+
+GALERKIN_KERNELS = ("galerkin0_ns", "galerkin0_ent", "galerkin_sys2_f32", "galerkin_sys2_bf16", "galerkin_sys3",
+                    "galerkin3_ns", "galerkin3_ent", "galerkin3_big")
+
+
+class force_galerkin_ns:
+    """Tests only (mof_test_force_galerkin_ns): multigrid setups inside the
+    block take the per-position Galerkin products k_galerkin0_ns /
+    k_galerkin3_ns where the by-entry ones would run."""
+
+    def __enter__(self):
+        L.check(L.lib().mof_test_force_galerkin_ns(1))
+        return self
+
+    def __exit__(self, *exc):
+        L.check(L.lib().mof_test_force_galerkin_ns(0))
+        return False
+
+
+def galerkin_launches() -> dict:
+    """Tests only (mof_test_galerkin_launches): launches so far in this process
+    of each Galerkin product kernel (``GALERKIN_KERNELS``)."""
+    c = np.zeros(len(GALERKIN_KERNELS), dtype=np.int64)
+    L.check(L.lib().mof_test_galerkin_launches(L.ptr(c)))
+    return {k: int(v) for k, v in zip(GALERKIN_KERNELS, c)}
+
+
+def amg_levels(mesh: "DeviceMesh", device=None) -> dict:
+    """Tests only (mof_test_amg_levels): the host multigrid hierarchy the
+    handle's preconditioner was built from (after a multigrid solve), as
+    ``{"regular", "omega", "omega1", "nc", "cap", "levels": [...]}``; each level
+    a dict of ``n, bs, sell_nb, smoothed, sym, has_Ah`` and the arrays
+    ``sell_off, sell_col, sell_row, diag_pos``, level 0 ``mirror``, levels >= 1
+    ``dead`` (n, 3) and ``twin``, and for the transition to the next level
+    ``agg, pptr, pcol, Q`` (P blocks, bs, 3), ``gptr, gent`` (terms, 3)."""
+    f = L.lib().mof_test_amg_levels
+    nl = ctypes.c_int32(0)
+    om = np.zeros(2, dtype=np.float32)
+    none = [None] * 13
+    out = {"levels": []}
+    with mesh.lock(device):
+        h = mesh.handle(device)
+        L.check(f(h, -1, ctypes.byref(nl), None, L.ptr(om), *none))
+        for l in range(nl.value):
+            sz = np.zeros(16, dtype=np.int64)
+            L.check(f(h, l, ctypes.byref(nl), L.ptr(sz), None, *none))
+            n, bs, nb = int(sz[0]), int(sz[1]), int(sz[2])
+            i32 = lambda k: np.zeros(int(k), dtype=np.int32)  # noqa: E731
+            lv = {"n": n, "bs": bs, "sell_nb": nb, "smoothed": bool(sz[4]), "sym": bool(sz[12]),
+                  "has_Ah": bool(sz[15]), "sell_off": i32(sz[3]), "sell_col": i32(nb), "sell_row": i32(nb),
+                  "diag_pos": i32(n), "dead": np.zeros((n, 3) if l else (0, 3), dtype=np.uint8),
+                  "twin": i32(nb if l else 0), "mirror": i32(0 if l else nb), "agg": i32(sz[5]), "pptr": i32(sz[6]),
+                  "pcol": i32(sz[7]), "Q": np.zeros((int(sz[8]) // (3 * bs), bs, 3), dtype=np.float32),
+                  "gptr": i32(sz[9]), "gent": np.zeros((int(sz[10]) // 3, 3), dtype=np.int32)}
+            p = lambda k: L.ptr(lv[k]) if lv[k].size else None  # noqa: E731
+            L.check(f(h, l, ctypes.byref(nl), None, None, p("sell_off"), p("sell_col"), p("sell_row"), p("diag_pos"),
+                      p("dead"), p("twin"), p("mirror"), p("agg"), p("pptr"), p("pcol"), p("Q"), p("gptr"),
+                      p("gent")))
+            out["levels"].append(lv)
+            out.update(regular=bool(sz[11]), nc=int(sz[13]), cap=int(sz[14]))
+    out.update(omega=float(om[0]), omega1=float(om[1]))
+    return out
+
+
+def amg_readback(mesh: "DeviceMesh", level: int, system: int, n: int, sell_nb: int, has_Ah: bool, nc: int = 0,
+                 device=None) -> dict:
+    """Tests only (mof_test_amg_readback): what the handle's last multigrid
+    setup left for ``system`` on coarse level ``level`` (its ``n``, ``sell_nb``
+    and ``has_Ah`` from ``amg_levels``): ``A`` (sell_nb, 3, 4) float32, ``Dh``
+    (n, 4) uint32 and ``Dh22`` (n,) uint16, with ``has_Ah`` the sweep copy ``Ah``
+    (sell_nb, 2) uint32 and ``Ah22`` (sell_nb, 2) uint16, and with ``nc`` > 0 (the
+    coarsest level) ``cinv`` (nc, nc) float32."""
+    r = {"A": np.zeros((sell_nb, 3, 4), dtype=np.float32), "Dh": np.zeros((n, 4), dtype=np.uint32),
+         "Dh22": np.zeros(n, dtype=np.uint16)}
+    if has_Ah:
+        r["Ah"] = np.zeros((sell_nb, 2), dtype=np.uint32)
+        r["Ah22"] = np.zeros((sell_nb, 2), dtype=np.uint16)
+    if nc:
+        r["cinv"] = np.zeros((nc, nc), dtype=np.float32)
+    p = lambda k: L.ptr(r[k]) if k in r else None  # noqa: E731
+    with mesh.lock(device):
+        L.check(L.lib().mof_test_amg_readback(mesh.handle(device), int(level), int(system), p("A"), p("Dh"),
+                                              p("Dh22"), p("Ah"), p("Ah22"), p("cinv")))
+    return r
