@@ -536,6 +536,50 @@ int mof_test_force_galerkin_ns(int32_t on);
  * k_galerkin0_ent, k_galerkin_sys<2> from the fp32 and from the bf16 slab,
  * k_galerkin_sys<3>, k_galerkin3_ns, k_galerkin3_ent and k_galerkin3_big. */
 int mof_test_galerkin_launches(int64_t *counts);
+/* Test hook: the production V-cycle (amg_vcycle, its own launches) applied to
+ * a given residual. The handle has just solved exactly one batch of B systems
+ * with the multigrid, so the batch's operators are live. r ([B][N][2] floats,
+ * internal order) goes into the inner solver's r; a kernel of the hook writes
+ * the pre-smoothed x0 = w D^-1 r of every system with the PCG's own
+ * expression; then the cycle runs over the nl systems smap lists (NULL: all
+ * B), skipping those flagged in retired ([B] bytes, or NULL; the handle's own
+ * per-system flags are saved and put back). zh: z as bf16 pairs (1), float2
+ * (0), the mesh's own choice (-1). tap != 0: the cycle also keeps level 0's
+ * iterate at four points (on entry, after the pre-sweep on the boundary ring,
+ * after the prolongation, after the post-sweep) -- copies between the
+ * launches, nothing else changes. sentinel (or NULL): the word z, level 0's
+ * r and fp32 iterate and every coarse vector are filled with beforehand.
+ * Out: z ([B][N][2] words; with zh the first B N hold the pairs), rz ([B]: the
+ * partial r.z records k_post0_ns wrote, summed in row-block order; 0 for a
+ * system the cycle skipped), and for each of the nsys systems listed r1 (N
+ * words: level 0's residual, bf16 pairs at the aggregates' member positions),
+ * taps ([4][N][2] words; a tap in the bf16 format fills N) and coarse (per
+ * level >= 1 its b, x, r, y, [n][4] floats each, r at the member positions).
+ * meta[0..4) = zh in force, xm (level 0's corrected iterate: 1 bf16 in place,
+ * 2 float2), the first level of the fused k_subcycle, row blocks per system.
+ * Any output but z may be NULL. */
+int mof_test_amg_vcycle(mof_mesh *mesh, int32_t B, const float *r, const int32_t *smap, int32_t nl,
+                        const uint8_t *retired, int32_t zh, int32_t tap, const uint32_t *sentinel, uint32_t *z,
+                        double *rz, int32_t nsys, const int32_t *systems, uint32_t *r1, uint32_t *taps,
+                        float *coarse, int32_t *meta);
+/* Test hook: what a reference of the cycle needs beside mof_test_amg_levels.
+ * sizes[0..12) = the lengths of apos, mptr, mlist, rptr, rent of `level`, xm,
+ * the mesh's own zh, the first fused level, then of the boundary ring its
+ * rows, sweeps per side and SELL slots, and the row blocks per system. apos
+ * (node -> position in its level's r), mptr / mlist (aggregate members), rptr /
+ * rent (a smoothed transition's restriction lists: pairs {fine node, P block}).
+ * bsw_rows (ring rows), bsw_bsrc (per ring slot the level-0 position its block
+ * comes from, | 1 << 30 transposed, -1 none) and bsw_A (the ring blocks of
+ * `system`, 2 words per slot) only on a handle with boundary sweeps. */
+int mof_test_amg_vcycle_tables(mof_mesh *mesh, int32_t level, int32_t system, int64_t *sizes, int32_t *apos,
+                               int32_t *mptr, int32_t *mlist, int32_t *rptr, int32_t *rent, int32_t *bsw_rows,
+                               int32_t *bsw_bsrc, uint32_t *bsw_A);
+/* Test hook: counts[0..25) = launches so far in this process of k_res0_ns
+ * (plain / mirrored, packed), k_restrict<2,2>, k_restrict<3>,
+ * k_restrict0_sa<2>, <3>, k_res3, k_subcycle, k_prolong<3>, k_prolong3_sa,
+ * k_prolong0<1>, <2>, k_prolong0_sa<1>, <2>, k_post3, k_bsweep<false>, <true>,
+ * and k_post0_ns<XM, ZH, 2, PK> at 17 + (XM - 1) * 4 + ZH * 2 + PK. */
+int mof_test_vcycle_launches(int64_t *counts);
 
 /* Diagnostic (host only): checks that the XCD-aware workgroup order of the
  * row kernels -- nblk row blocks x batch systems, walked in groups of

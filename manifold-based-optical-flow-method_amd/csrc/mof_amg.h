@@ -173,6 +173,10 @@ struct AmgDevice {
     // regular meshes) (k_a_slab -> k_galerkin_sys<2>), reused slab by slab
     DevArray<float> aslab;
     bool bf16_fresh = false;  // A0h written by the batch's assembly
+    // plain-read single-domain meshes: level 0's mirror table (the hierarchy's),
+    // by which each batch's lower blocks of A0h become their upper twins
+    // transposed (k_h0_twins); empty under symmetric reads
+    DevArray<int32_t> mir0;
     // the host hierarchy the levels above were uploaded from (amg_build;
     // mof_test_amg_levels exports it)
     std::shared_ptr<const AmgHierarchy> H;

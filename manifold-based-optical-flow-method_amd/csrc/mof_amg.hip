@@ -46,6 +46,14 @@ std::atomic<int> g_force_galerkin_ns{0};
 // launches so far (mof_test_galerkin_launches), in this order
 enum GalKernel { kGal0Ns, kGal0Ent, kGalSys2F32, kGalSys2Bf16, kGalSys3, kGal3Ns, kGal3Ent, kGal3Big, kGalKernels };
 std::atomic<int64_t> g_galerkin_launches[kGalKernels];
+// launches so far of each V-cycle kernel instance (mof_test_vcycle_launches),
+// in this order; k_post0_ns's eight from kVcPost0: (XM - 1) * 4 + ZH * 2 + PK
+enum VcKernel {
+    kVcRes0, kVcRes0Pk, kVcRestrict2, kVcRestrict3, kVcRestrict0Sa2, kVcRestrict0Sa3, kVcRes3, kVcSubcycle,
+    kVcProlong3, kVcProlong3Sa, kVcProlong0X1, kVcProlong0X2, kVcProlong0SaX1, kVcProlong0SaX2, kVcPost3,
+    kVcBsweepH, kVcBsweepF, kVcPost0, kVcKernels = kVcPost0 + 8
+};
+std::atomic<int64_t> g_vcycle_launches[kVcKernels];
 
 namespace {
 
@@ -218,6 +226,24 @@ __global__ __launch_bounds__(kWG) void k_to_h0(int64_t n, const float4 *__restri
     if (q >= n) return;
     const float4 v = A[q];
     h0_st(H, q, v.x, v.y, v.z, v.w);
+}
+
+// Plain-read meshes: the assembly forms a lower block (i, j), j < i, on its
+// own, and now and then it rounds to another bf16 than its upper twin (one
+// bf16 ulp on a few blocks of a 3,000-vertex hull); the sweeps read every
+// block at its own position, so the smoother's operator -- and the V-cycle --
+// would be symmetric only to that rounding. Each lower block of the sweep copy
+// becomes its upper twin transposed, through the mirror table the level-0
+// gather lists already read by (symmetric-read meshes read that way anyway).
+// Grid (position blocks, systems).
+__global__ __launch_bounds__(kWG) void k_h0_twins(int64_t nb, const int32_t *__restrict__ mir,
+                                                  uint2 *__restrict__ H) {
+    const int64_t p = (int64_t)blockIdx.x * kWG + threadIdx.x;
+    if (p >= nb) return;
+    const int32_t mr = mir[p];
+    if (mr < 0 || !(mr & kMirT)) return;  // padding, the diagonal and upper blocks
+    const int64_t o = (int64_t)blockIdx.y * nb;
+    H[o + p] = h0_tr(h0_ld(H, o + (mr & kMirPos)));
 }
 
 // Level 0's Galerkin product with kNS systems per thread: the gather entry
@@ -1866,12 +1892,14 @@ template <bool F32X>
 void launch_bsweep(const AmgDevice &G, SysMap sm, const float *rv, float *xv, float omega, const int32_t *sysi,
                    hipStream_t s) {
     const size_t lds = sizeof(float2) * (2 * (size_t)G.bsw_n + G.bsw_nout);
+    ++g_vcycle_launches[F32X ? kVcBsweepF : kVcBsweepH];
     k_bsweep<F32X><<<dim3((unsigned)sm.n), kBswWG, lds, s>>>(bsw_args(G), sm, rv, xv, omega, G.bsw_sweeps, sysi);
 }
 
 template <int XM, bool ZH, typename... Args>
 void launch_post0(bool packed, int32_t nblk, int32_t B, hipStream_t s, Args... args) {
     const dim3 g(xcd_grid(nblk, (B + kPost0NS - 1) / kPost0NS, kGrpSmooth > kPost0NS ? kGrpSmooth / kPost0NS : 1));
+    ++g_vcycle_launches[kVcPost0 + (XM - 1) * 4 + (ZH ? 2 : 0) + (packed ? 1 : 0)];
     if (packed)
         k_post0_ns<XM, ZH, kPost0NS, true><<<g, kWG, 0, s>>>(args...);
     else
@@ -2069,6 +2097,7 @@ bool amg_build(mof_mesh *m) {
         d.alloc(h.size());
         if (!h.empty()) d.upload(h.data(), h.size(), s);
     };
+    if (!m->sym_reads && m->n_own == m->N) put_i(G.mir0, H.mirror);  // k_h0_twins
     // open surfaces: the boundary rows (fewer incident triangles than
     // neighbours: the diagonal block's contribution list has one entry per
     // incident triangle) and one ring of their neighbours, for k_bsweep: 2
@@ -2369,6 +2398,12 @@ void amg_setup_batch(mof_mesh *m, int32_t B, hipStream_t s) {
             nb0, reinterpret_cast<const float4 *>(w.A32.p), reinterpret_cast<uint2 *>(G.A0h.p));
     }
     G.bf16_fresh = false;
+    if (G.mir0.n > 1) {
+        const int64_t nb = m->pat.sell_nb();
+        MOF_REQUIRE((int64_t)G.mir0.n == nb, "level 0's mirror table does not fit the mesh");
+        k_h0_twins<<<dim3((unsigned)((nb + kWG - 1) / kWG), (unsigned)B), kWG, 0, s>>>(
+            nb, G.mir0.p, reinterpret_cast<uint2 *>(G.A0h.p));
+    }
     if (G.bsw_n > 0) {
         const int64_t n = (int64_t)G.bsw_nslot * B;
         k_bsw_extract<<<dim3((unsigned)((n + kWG - 1) / kWG)), kWG, 0, s>>>(
@@ -2501,7 +2536,7 @@ Lvl level_view(const AmgDevLevel &D) {
 }
 
 void amg_vcycle(mof_mesh *m, int32_t B, const float *r0, float *z0, double *part_slot, int32_t nblk,
-                const RedArgs &rd, hipStream_t s, bool zh, const int32_t *smap, int32_t nl) {
+                const RedArgs &rd, hipStream_t s, bool zh, const int32_t *smap, int32_t nl, float *tap) {
     AmgDevice &G = *m->amg;
     Workspace &w = m->ws;
     const int32_t L = (int32_t)G.lv.size();
@@ -2520,6 +2555,16 @@ void amg_vcycle(mof_mesh *m, int32_t B, const float *r0, float *z0, double *part
     // levels S.. run fused in k_subcycle
     int32_t S = 1;
     while (S < L - 1 && G.lv[S].n > kSubNodes) ++S;
+    // tests only (mof_test_amg_vcycle; null in production): level 0's iterate
+    // of all B systems copied to tap[k] (2 B N floats each) before the
+    // in-place updates overwrite it -- stream-ordered copies between the
+    // launches, which do not depend on them
+    auto tap_x = [&](int k, const float *x, size_t words_per_vertex) {
+        if (!tap) return;
+        MOF_HIP(hipMemcpyAsync(tap + (size_t)k * 2 * B * v[0].n, x, sizeof(float) * words_per_vertex * B * v[0].n,
+                               hipMemcpyDeviceToDevice, s));
+    };
+    tap_x(0, v[0].x, 1);
     // the cycle below level 0 from level 1's restricted b and pre-smoothed
     // x: down (residual, restriction + next pre-smooth), the fused tiny
     // levels, up (prolongation, post-smoothing into y)
@@ -2527,6 +2572,8 @@ void amg_vcycle(mof_mesh *m, int32_t B, const float *r0, float *z0, double *part
         for (int32_t l = 1; l < S; ++l) {
             const int32_t smooth = l + 1 < L - 1;
             k_res3<<<grid2(u[l].n, nL), kWG, 0, s>>>(u[l], sysi);
+            ++g_vcycle_launches[kVcRes3];
+            ++g_vcycle_launches[G.lv[l].smoothed ? kVcRestrict0Sa3 : kVcRestrict3];
             if (G.lv[l].smoothed)
                 k_restrict0_sa<3><<<dim3(xcd_grid(G.lv[l].ngrp, (nL + kNSR - 1) / kNSR, kGrpRestr)), kWG, 0, s>>>(
                     u[l], u[l + 1], G.lv[l].rgrp.p, G.lv[l].ngrp, B, smooth, om1, sysi);
@@ -2542,7 +2589,10 @@ void amg_vcycle(mof_mesh *m, int32_t B, const float *r0, float *z0, double *part
         sa.omega = om1;
         sa.sysi = sysi;
         k_subcycle<<<dim3((unsigned)nL), kSubWG, 0, s>>>(sa);
+        ++g_vcycle_launches[kVcSubcycle];
         for (int32_t l = S - 1; l >= 1; --l) {
+            ++g_vcycle_launches[G.lv[l].smoothed ? kVcProlong3Sa : kVcProlong3];
+            ++g_vcycle_launches[kVcPost3];
             if (G.lv[l].smoothed) {
                 const int32_t nb = (u[l].n + kWG - 1) / kWG;
                 k_prolong3_sa<<<dim3(xcd_grid(nb, (nL + kNS3 - 1) / kNS3, kGrpProl)), kWG, 0, s>>>(u[l], u[l + 1], nb,
@@ -2559,6 +2609,9 @@ void amg_vcycle(mof_mesh *m, int32_t B, const float *r0, float *z0, double *part
         const int32_t smooth = l + 1 < L - 1;
         if (l == 0) {
             if (G.bsw_n > 0) launch_bsweep<false>(G, sm, r0, v[0].x, om, sysi, s);
+            tap_x(1, v[0].x, 1);
+            ++g_vcycle_launches[mat0.sell_idx ? kVcRes0Pk : kVcRes0];
+            ++g_vcycle_launches[G.lv[0].smoothed ? kVcRestrict0Sa2 : kVcRestrict2];
             const dim3 gr(xcd_grid(nblk, (nL + kRes0NS - 1) / kRes0NS, kGrpSmooth > kRes0NS ? kGrpSmooth / kRes0NS : 1));
             (mat0.sell_idx ? k_res0_ns<kRes0NS, true> : k_res0_ns<kRes0NS, false>)<<<gr, kWG, 0, s>>>(
                 v[0].n, nblk, B, sm, mat0, r0, v[0].x, G.lv[0].smoothed ? nullptr : v[0].apos, sysi, v[0].r);
@@ -2580,6 +2633,7 @@ void amg_vcycle(mof_mesh *m, int32_t B, const float *r0, float *z0, double *part
         sa.omega = om1;
         sa.sysi = sysi;
         k_subcycle<<<dim3((unsigned)nL), kSubWG, 0, s>>>(sa);
+        ++g_vcycle_launches[kVcSubcycle];
     } else {
         coarse(v);
     }
@@ -2589,12 +2643,15 @@ void amg_vcycle(mof_mesh *m, int32_t B, const float *r0, float *z0, double *part
             const int32_t nb0 = (v[0].n + kWG - 1) / kWG;
             const int32_t nb0p = (v[0].n + kWG * kProlR - 1) / (kWG * kProlR);
             const dim3 gsa(xcd_grid(nb0, (nL + kNSP - 1) / kNSP, kGrpProl)), gp(xcd_grid(nb0p, (nL + kProlS - 1) / kProlS, kGrpProl));
+            ++g_vcycle_launches[(G.lv[0].smoothed ? kVcProlong0SaX1 : kVcProlong0X1) + (G.xm == 2 ? 1 : 0)];
             if (G.xm == 2) {
                 if (G.lv[0].smoothed)
                     k_prolong0_sa<2><<<gsa, kWG, 0, s>>>(v[0], v[1], nb0, B, sysi);
                 else
                     k_prolong0<2><<<gp, kWG, 0, s>>>(v[0], v[1], nb0p, B, sysi);
+                tap_x(2, v[0].y, 2);
                 if (G.bsw_n > 0) launch_bsweep<true>(G, sm, r0, v[0].y, om, sysi, s);
+                tap_x(3, v[0].y, 2);
                 if (zh)
                     launch_post0<2, true>(mat0.sell_idx != nullptr, nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, v[0].y, om, sysi, z0, part_slot, rd);
                 else
@@ -2604,7 +2661,9 @@ void amg_vcycle(mof_mesh *m, int32_t B, const float *r0, float *z0, double *part
                     k_prolong0_sa<1><<<gsa, kWG, 0, s>>>(v[0], v[1], nb0, B, sysi);
                 else
                     k_prolong0<1><<<gp, kWG, 0, s>>>(v[0], v[1], nb0p, B, sysi);
+                tap_x(2, v[0].x, 1);
                 if (G.bsw_n > 0) launch_bsweep<false>(G, sm, r0, v[0].x, om, sysi, s);
+                tap_x(3, v[0].x, 1);
                 if (zh)
                     launch_post0<1, true>(mat0.sell_idx != nullptr, nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, v[0].x, om, sysi, z0, part_slot, rd);
                 else
@@ -2634,6 +2693,35 @@ struct DeviceGuard {
         MOF_HIP(hipSetDevice(d));
     }
     ~DeviceGuard() { (void)hipSetDevice(prev); }
+};
+
+// tests only (mof_test_amg_vcycle): the level-0 pre-smoothing x0 = w D^-1 r
+// of every system, the expression of k_pcg_init / k_pcg_update
+__global__ __launch_bounds__(kWG) void k_test_presmooth(int32_t N, const uint2 *__restrict__ dA, int64_t dA_nb,
+                                                        const int32_t *__restrict__ dA_off,
+                                                        const float *__restrict__ r, float omega,
+                                                        float *__restrict__ x0) {
+    const int32_t i = blockIdx.x * kWG + threadIdx.x, b = blockIdx.y;
+    const int64_t vi = (int64_t)b * N + min(i, N - 1);
+    const float2 ri = reinterpret_cast<const float2 *>(r)[vi];
+    const float2 d = bf16_diag_solve(bf16_diag_block(dA, dA_nb, dA_off, b, min(i, N - 1)), ri.x, ri.y);
+    if (i < N) st_x0(x0, vi, omega * d.x, omega * d.y);
+}
+
+// the handle's per-system flags replaced for one test cycle and put back
+struct SysiSwap {
+    int32_t *dev;
+    std::vector<int32_t> saved;
+    SysiSwap(int32_t *d, int32_t B, const uint8_t *retired_mask) : dev(d), saved((size_t)B * kSysStride) {
+        MOF_HIP(hipMemcpy(saved.data(), dev, saved.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        std::vector<int32_t> now(saved.size(), 0);
+        for (int32_t b = 0; b < B; ++b) {
+            now[(size_t)b * kSysStride + SI_CONV] = -1;
+            now[(size_t)b * kSysStride + SI_ACTIVE] = !(retired_mask && retired_mask[b]);
+        }
+        MOF_HIP(hipMemcpy(dev, now.data(), now.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    ~SysiSwap() { (void)hipMemcpy(dev, saved.data(), saved.size() * sizeof(int32_t), hipMemcpyHostToDevice); }
 };
 }  // namespace
 
@@ -2760,6 +2848,152 @@ int mof_test_galerkin_launches(int64_t *counts) {
     return mof_io_guard([&] {
         MOF_REQUIRE(counts, "NULL argument");
         for (int k = 0; k < mof::kGalKernels; ++k) counts[k] = mof::g_galerkin_launches[k].load();
+    });
+}
+
+int mof_test_vcycle_launches(int64_t *counts) {
+    return mof_io_guard([&] {
+        MOF_REQUIRE(counts, "NULL argument");
+        for (int k = 0; k < mof::kVcKernels; ++k) counts[k] = mof::g_vcycle_launches[k].load();
+    });
+}
+
+int mof_test_amg_vcycle_tables(mof_mesh *m, int32_t level, int32_t system, int64_t *sizes, int32_t *apos,
+                               int32_t *mptr, int32_t *mlist, int32_t *rptr, int32_t *rent, int32_t *bsw_rows,
+                               int32_t *bsw_bsrc, uint32_t *bsw_A) {
+    return mof_io_guard([&] {
+        MOF_REQUIRE(m, "mesh is NULL");
+        mof::mesh_join_prep(m);
+        mof::AmgDevice *G = m->amg;
+        MOF_REQUIRE(G && G->built && G->H && G->lv.size() >= 2 && G->H->levels.size() == G->lv.size(),
+                    "the handle has no built multigrid");
+        const int32_t L = (int32_t)G->lv.size();
+        MOF_REQUIRE(level >= 0 && level < L, "no such level");
+        const mof::AmgLevel &H = G->H->levels[level];
+        int32_t S = 1;
+        while (S < L - 1 && G->lv[S].n > mof::kSubNodes) ++S;
+        if (sizes) {
+            const int64_t v[12] = {(int64_t)H.apos.size(), (int64_t)H.mptr.size(), (int64_t)H.mlist.size(),
+                                   (int64_t)H.rptr.size(), (int64_t)H.rent.size(), G->xm, G->regular, S,
+                                   G->bsw_n, G->bsw_sweeps, G->bsw_nslot, m->ws.nblk};
+            std::copy(v, v + 12, sizes);
+        }
+        auto put = [](int32_t *dst, const std::vector<int32_t> &src) {
+            if (dst) std::copy(src.begin(), src.end(), dst);
+        };
+        put(apos, H.apos);
+        put(mptr, H.mptr);
+        put(mlist, H.mlist);
+        put(rptr, H.rptr);
+        put(rent, H.rent);
+        if (!(bsw_rows || bsw_bsrc || bsw_A)) return;
+        MOF_REQUIRE(G->bsw_n > 0, "the handle runs no boundary sweeps");
+        MOF_REQUIRE(system >= 0 && system < G->cap, "no multigrid storage for that system");
+        mof::DeviceGuard dg(m->device);
+        MOF_HIP(hipStreamSynchronize(m->stream));
+        if (bsw_rows)
+            MOF_HIP(hipMemcpy(bsw_rows, G->bsw_rows.p, sizeof(int32_t) * G->bsw_n, hipMemcpyDeviceToHost));
+        if (bsw_bsrc)
+            MOF_HIP(hipMemcpy(bsw_bsrc, G->bsw_bsrc.p, sizeof(int32_t) * G->bsw_nslot, hipMemcpyDeviceToHost));
+        if (bsw_A)
+            MOF_HIP(hipMemcpy(bsw_A, G->bsw_A.p + (size_t)2 * G->bsw_nslot * system,
+                              sizeof(uint32_t) * 2 * G->bsw_nslot, hipMemcpyDeviceToHost));
+    });
+}
+
+int mof_test_amg_vcycle(mof_mesh *m, int32_t B, const float *r, const int32_t *smap, int32_t nl,
+                        const uint8_t *retired, int32_t zh, int32_t tap, const uint32_t *sentinel, uint32_t *z,
+                        double *rz, int32_t nsys, const int32_t *systems, uint32_t *r1, uint32_t *taps,
+                        float *coarse, int32_t *meta) {
+    return mof_io_guard([&] {
+        MOF_REQUIRE(m && r && z, "NULL argument");
+        mof::mesh_join_prep(m);
+        mof::AmgDevice *Gp = m->amg;
+        MOF_REQUIRE(Gp && Gp->built && Gp->lv.size() >= 2, "the handle has no built multigrid");
+        mof::AmgDevice &G = *Gp;
+        mof::Workspace &w = m->ws;
+        MOF_REQUIRE(B >= 1 && B <= G.cap && B <= w.cap, "the handle's last batch had fewer systems");
+        MOF_REQUIRE(m->n_own == m->N, "a decomposed part's handle");
+        MOF_REQUIRE(!smap || (nl >= 1 && nl <= B), "bad system map");
+        for (int32_t l = 0; smap && l < nl; ++l) MOF_REQUIRE(smap[l] >= 0 && smap[l] < B, "bad system map");
+        for (int32_t k = 0; k < nsys; ++k)
+            MOF_REQUIRE(systems && systems[k] >= 0 && systems[k] < B, "bad system to read back");
+        const bool zhb = zh < 0 ? G.regular : zh != 0;
+        const int32_t L = (int32_t)G.lv.size();
+        const size_t N = (size_t)m->N, nv = N * B;
+        mof::DeviceGuard dg(m->device);
+        hipStream_t s = m->stream;
+        MOF_HIP(hipStreamSynchronize(s));
+        float *rv = reinterpret_cast<float *>(w.vr.p), *zv = reinterpret_cast<float *>(w.vz.p);
+        MOF_HIP(hipMemcpy(rv, r, sizeof(float) * 2 * nv, hipMemcpyHostToDevice));
+        mof::SysiSwap swap(w.sysi.p, B, retired);
+        const mof::AmgFine f = mof::amg_fine(m);
+        mof::k_test_presmooth<<<mof::grid2((int64_t)N, B), mof::kWG, 0, s>>>(
+            (int32_t)N, static_cast<const uint2 *>(f.A0h), f.sell_nb, f.sell_off, rv, f.omega, f.x0);
+        auto fill = [&](void *p, size_t words) {
+            if (sentinel) MOF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p), (int)*sentinel, words, s));
+        };
+        fill(zv, 2 * nv);
+        fill(G.lv[0].r.p, nv);
+        if (G.xm == 2) fill(G.lv[0].y.p, 2 * nv);
+        for (int32_t l = 1; l < L; ++l) {
+            mof::AmgDevLevel &D = G.lv[l];
+            for (mof::DevArray<float> *a : {&D.b, &D.x, &D.r, &D.y}) fill(a->p, (size_t)4 * D.n * B);
+        }
+        mof::DevArray<int32_t> dmap;
+        if (smap) {
+            dmap.alloc((size_t)nl);
+            MOF_HIP(hipMemcpyAsync(dmap.p, smap, sizeof(int32_t) * nl, hipMemcpyHostToDevice, s));
+        }
+        mof::DevArray<float> dtap;
+        if (tap) {
+            dtap.alloc(8 * nv);
+            dtap.zero(s);
+        }
+        const size_t nrec = (size_t)2 * B * w.nblk;
+        MOF_REQUIRE(w.part_rzrr.n >= nrec, "partial records smaller than the batch");
+        MOF_HIP(hipMemsetAsync(w.part_rzrr.p, 0, sizeof(double) * nrec, s));
+        mof::amg_vcycle(m, B, rv, zv, w.part_rzrr.p, w.nblk, mof::RedArgs{1, 0, w.nblk, m->N}, s, zhb,
+                        smap ? dmap.p : nullptr, nl, tap ? dtap.p : nullptr);
+        MOF_HIP(hipStreamSynchronize(s));
+        MOF_HIP(hipMemcpy(z, zv, sizeof(uint32_t) * (zhb ? 1 : 2) * nv, hipMemcpyDeviceToHost));
+        if (rz) {
+            std::vector<double> part(nrec);
+            MOF_HIP(hipMemcpy(part.data(), w.part_rzrr.p, sizeof(double) * nrec, hipMemcpyDeviceToHost));
+            for (int32_t b = 0; b < B; ++b) {
+                double t = 0.0;
+                for (int32_t k = 0; k < w.nblk; ++k) t += part[2 * ((size_t)b * w.nblk + k)];
+                rz[b] = t;
+            }
+        }
+        if (meta) {
+            int32_t S = 1;
+            while (S < L - 1 && G.lv[S].n > mof::kSubNodes) ++S;
+            const int32_t v[4] = {zhb, G.xm, S, w.nblk};
+            std::copy(v, v + 4, meta);
+        }
+        size_t per = 0;
+        for (int32_t l = 1; l < L; ++l) per += (size_t)16 * G.lv[l].n;
+        for (int32_t k = 0; k < nsys; ++k) {
+            const size_t b = (size_t)systems[k];
+            if (r1)
+                MOF_HIP(hipMemcpy(r1 + k * N, G.lv[0].r.p + b * N, sizeof(uint32_t) * N, hipMemcpyDeviceToHost));
+            // a tap's words of system b: N (the x0 format) or 2 N (float2) from its 2 B N
+            for (int t = 0; t < 4 && taps && tap; ++t) {
+                const size_t wpv = t >= 2 && G.xm == 2 ? 2 : 1;
+                MOF_HIP(hipMemcpy(taps + (4 * k + t) * 2 * N, dtap.p + t * 2 * nv + b * wpv * N,
+                                  sizeof(uint32_t) * wpv * N, hipMemcpyDeviceToHost));
+            }
+            float *o = coarse ? coarse + k * per : nullptr;
+            for (int32_t l = 1; l < L && o; ++l) {
+                mof::AmgDevLevel &D = G.lv[l];
+                const size_t n4 = (size_t)4 * D.n;
+                for (mof::DevArray<float> *a : {&D.b, &D.x, &D.r, &D.y}) {
+                    MOF_HIP(hipMemcpy(o, a->p + b * n4, sizeof(float) * n4, hipMemcpyDeviceToHost));
+                    o += n4;
+                }
+            }
+        }
     });
 }
 

@@ -396,8 +396,8 @@ __global__ __launch_bounds__(kWG) void k_assemble_mixed(
         const bool g = i >= nown || vcol[p] >= nown;
         if (g)
             h0_st(Ah, q, diag ? 1.f : 0.f, 0.f, 0.f, diag ? 1.f : 0.f);
-        else
-            h0_st(Ah, q, Av[0], Av[1], Av[2], Av[3]);
+        else  // a diagonal block keeps its upper entry for both halves (row_slot_store)
+            h0_st(Ah, q, Av[0], Av[1], diag ? Av[1] : Av[2], Av[3]);
     }
     if (!diag) return;
     // f_i in fp64, in the reference's triangle order
@@ -453,7 +453,12 @@ __device__ __forceinline__ void row_slot_store(const float (&acc)[4], float4 s4,
         if (ghost)
             h0_st(Ah, qq, diag ? 1.f : 0.f, 0.f, 0.f, diag ? 1.f : 0.f);
         else
-            h0_st(Ah, qq, Av[0], Av[1], Av[2], Av[3]);
+            // a diagonal block keeps its upper entry for both halves: a01 and
+            // a10 are the same sum in two orders and can round to different
+            // bf16, and the smoother's D (bf16_diag_solve) and with it the
+            // V-cycle would no longer be symmetric (1.6e-7 of the cycle's norm
+            // on one of three systems looked at of a 642-vertex sphere)
+            h0_st(Ah, qq, Av[0], Av[1], diag ? Av[1] : Av[2], Av[3]);
     }
     if (!diag) return;
     double inv[4];

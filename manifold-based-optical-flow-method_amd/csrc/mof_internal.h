@@ -524,8 +524,11 @@ void amg_setup_batch(mof_mesh *m, int32_t B, hipStream_t s);  // Galerkin + coar
 // zh: write z as a bf16 pair per vertex (uint32) instead of float2
 // smap / nl: the launches cover the nl systems smap lists (the PCG's tail
 // iterations), or all B when smap is null
+// tap: tests only (null in production), [4][B][N][2] floats: level 0's iterate
+// on entry, after the pre-sweep, after the prolongation, after the post-sweep
 void amg_vcycle(mof_mesh *m, int32_t B, const float *r, float *z, double *part_slot, int32_t nblk,
-                const RedArgs &rd, hipStream_t s, bool zh, const int32_t *smap = nullptr, int32_t nl = 0);
+                const RedArgs &rd, hipStream_t s, bool zh, const int32_t *smap = nullptr, int32_t nl = 0,
+                float *tap = nullptr);
 // level-0 smoother data the PCG update / init write the pre-smoothing with
 struct AmgFine {
     const void *A0h;  // bf16 level-0 operator [B][sell_nb] (its diagonal blocks give the smoother's D)

@@ -65,6 +65,7 @@ EXPORTS = (
     "mof_test_assembly_readback", "mof_winding_rings", "mof_winding_levels", "mof_winding_map",
     "mof_test_winding_pass", "mof_winding_timing", "mof_closest_vertices",
     "mof_test_amg_levels", "mof_test_amg_readback", "mof_test_force_galerkin_ns", "mof_test_galerkin_launches",
+    "mof_test_amg_vcycle", "mof_test_amg_vcycle_tables", "mof_test_vcycle_launches",
 )
 
 
@@ -217,6 +218,9 @@ def lib():
             "mof_test_amg_readback": ([P, i32, i32, P, P, P, P, P, P], ctypes.c_int),
             "mof_test_force_galerkin_ns": ([i32], ctypes.c_int),
             "mof_test_galerkin_launches": ([P], ctypes.c_int),
+            "mof_test_amg_vcycle": ([P, i32, P, P, i32, P, i32, i32, P, P, P, i32, P, P, P, P, P], ctypes.c_int),
+            "mof_test_amg_vcycle_tables": ([P, i32, i32] + [P] * 9, ctypes.c_int),
+            "mof_test_vcycle_launches": ([P], ctypes.c_int),
             "mof_xcd_map_check": ([i32, i32, i32], ctypes.c_int),
             "mof_xcd_batch_cap": ([i64, i32, P], ctypes.c_int),
             "mof_singularities_compact": ([i32, P, P, i32, i32, P, i32, f64, u32, P, i64, P, P, P, P, P,

@@ -531,3 +531,109 @@ def amg_readback(mesh: "DeviceMesh", level: int, system: int, n: int, sell_nb: i
         L.check(L.lib().mof_test_amg_readback(mesh.handle(device), int(level), int(system), p("A"), p("Dh"),
                                               p("Dh22"), p("Ah"), p("Ah22"), p("cinv")))
     return r
+
+
+VCYCLE_KERNELS = ("res0_ns", "res0_ns_pk", "restrict2", "restrict3", "restrict0_sa2", "restrict0_sa3", "res3",
+                  "subcycle", "prolong3", "prolong3_sa", "prolong0_x1", "prolong0_x2", "prolong0_sa_x1",
+                  "prolong0_sa_x2", "post3", "bsweep_h", "bsweep_f") + tuple(
+    "post0_x%d_%s%s" % (xm, "zh" if zh else "zf", "_pk" if pk else "")
+    for xm in (1, 2) for zh in (0, 1) for pk in (0, 1))
+
+
+def vcycle_launches() -> dict:
+    """Tests only (mof_test_vcycle_launches): launches so far in this process
+    of each V-cycle kernel instance (``VCYCLE_KERNELS``; ``post0_x<XM>_<zh|zf>[_pk]``
+    are k_post0_ns's eight)."""
+    c = np.zeros(len(VCYCLE_KERNELS), dtype=np.int64)
+    L.check(L.lib().mof_test_vcycle_launches(L.ptr(c)))
+    return {k: int(v) for k, v in zip(VCYCLE_KERNELS, c)}
+
+
+def amg_vcycle_tables(mesh: "DeviceMesh", n_levels: int, system: int = 0, device=None) -> dict:
+    """Tests only (mof_test_amg_vcycle_tables): ``xm``, ``zh`` (the mesh's own
+    choice), ``S`` (the first level inside k_subcycle), ``nblk``, per level
+    ``apos, mptr, mlist, rptr, rent`` (``levels``), and on a handle with
+    boundary sweeps ``bsw_rows``, ``bsw_sweeps``, ``bsw_bsrc`` and ``bsw_A``
+    (slots, 2) uint32, the ring blocks of ``system``."""
+    f = L.lib().mof_test_amg_vcycle_tables
+    out = {"levels": []}
+    none = [None] * 8
+    with mesh.lock(device):
+        h = mesh.handle(device)
+        for l in range(n_levels):
+            sz = np.zeros(12, dtype=np.int64)
+            L.check(f(h, l, int(system), L.ptr(sz), *none))
+            t = {k: np.zeros(int(sz[i]), dtype=np.int32) for i, k in enumerate(("apos", "mptr", "mlist", "rptr", "rent"))}
+            p = lambda k: L.ptr(t[k]) if t[k].size else None  # noqa: E731
+            L.check(f(h, l, int(system), None, p("apos"), p("mptr"), p("mlist"), p("rptr"), p("rent"), None, None, None))
+            t["rent"] = t["rent"].reshape(-1, 2)
+            out["levels"].append(t)
+        out.update(xm=int(sz[5]), zh=bool(sz[6]), S=int(sz[7]), bsw_n=int(sz[8]), bsw_sweeps=int(sz[9]),
+                   nblk=int(sz[11]))
+        if out["bsw_n"]:
+            out["bsw_rows"] = np.zeros(int(sz[8]), dtype=np.int32)
+            out["bsw_bsrc"] = np.zeros(int(sz[10]), dtype=np.int32)
+            out["bsw_A"] = np.zeros((int(sz[10]), 2), dtype=np.uint32)
+            L.check(f(h, 0, int(system), None, None, None, None, None, None, L.ptr(out["bsw_rows"]),
+                      L.ptr(out["bsw_bsrc"]), L.ptr(out["bsw_A"])))
+    return out
+
+
+def amg_vcycle(mesh: "DeviceMesh", r, level_sizes, systems=(), smap=None, retired=None, zh=None, tap=False,
+               sentinel=None, device=None) -> dict:
+    """Tests only (mof_test_amg_vcycle): the production V-cycle of the handle's
+    last multigrid batch applied to ``r`` (B, N, 2) float32 in the internal
+    order, over the systems ``smap`` lists (all B without) except those flagged
+    in ``retired`` (B,); ``zh`` forces z's format (None: the mesh's own);
+    ``tap`` keeps level 0's iterate at four points; ``sentinel`` is the word
+    the cycle's outputs are filled with beforehand. ``level_sizes``: every
+    level's ``n`` (amg_levels). Returns ``zh, xm, S, nblk``, ``z_words`` (B, N
+    [, 2]) uint32, ``z`` (B, N, 2) float32 decoded, ``rz`` (B,), and per system
+    read back ``r1`` (N,) uint32, ``taps`` (level 0's iterate on entry, after
+    the pre-sweep, after the prolongation, after the post-sweep: (N,) uint32
+    in the bf16 pair format, the last two (N, 2) float32 words with xm = 2;
+    empty without ``tap``) and ``coarse``: per level >= 1 a dict of ``b, x, r,
+    y`` (n, 4) float32."""
+    r = np.ascontiguousarray(r, dtype=np.float32)
+    B, N = r.shape[0], r.shape[1]
+    assert r.shape == (B, N, 2)
+    systems = np.ascontiguousarray(systems, dtype=np.int32)
+    ns = len(systems)
+    per = sum(16 * int(n) for n in level_sizes[1:])
+    z = np.zeros((B, N, 2), dtype=np.uint32)
+    rz = np.zeros(B, dtype=np.float64)
+    r1 = np.zeros((ns, N), dtype=np.uint32)
+    taps = np.zeros((ns, 4, N, 2), dtype=np.uint32)
+    coarse = np.zeros((ns, per), dtype=np.float32)
+    meta = np.zeros(4, dtype=np.int32)
+    sm = None if smap is None else np.ascontiguousarray(smap, dtype=np.int32)
+    rt = None if retired is None else np.ascontiguousarray(retired, dtype=np.uint8)
+    assert rt is None or rt.shape == (B,)
+    sw = None if sentinel is None else np.array([sentinel], dtype=np.uint32)
+    o = lambda a: None if a is None else L.ptr(a)  # noqa: E731
+    with mesh.lock(device):
+        L.check(L.lib().mof_test_amg_vcycle(mesh.handle(device), B, L.ptr(r), o(sm), 0 if sm is None else len(sm), o(rt),
+                                            -1 if zh is None else int(bool(zh)), int(bool(tap)), o(sw), L.ptr(z),
+                                            L.ptr(rz), ns, o(systems) if ns else None, L.ptr(r1), L.ptr(taps),
+                                            L.ptr(coarse), L.ptr(meta)))
+    out = {"zh": bool(meta[0]), "xm": int(meta[1]), "S": int(meta[2]), "nblk": int(meta[3]), "rz": rz, "sys": {}}
+    if out["zh"]:
+        w = z.reshape(-1)[:B * N].reshape(B, N)
+        out["z_words"] = w.copy()
+        out["z"] = np.stack([(w << np.uint32(16)).view(np.float32), (w & np.uint32(0xFFFF0000)).view(np.float32)], axis=-1)
+    else:
+        out["z_words"] = z
+        out["z"] = z.view(np.float32)
+    for k, s in enumerate(systems):
+        lev, q = [None], 0
+        for n in level_sizes[1:]:
+            d = {}
+            for name in ("b", "x", "r", "y"):
+                d[name] = coarse[k, q:q + 4 * n].reshape(n, 4).copy()
+                q += 4 * n
+            lev.append(d)
+        # a tap in the bf16 pair format fills the first N words of its slot
+        tp = [taps[k, t].copy() if t >= 2 and out["xm"] == 2 else taps[k, t].reshape(-1)[:N].copy()
+              for t in range(4)] if tap else []
+        out["sys"][int(s)] = {"r1": r1[k].copy(), "taps": tp, "coarse": lev}
+    return out
