@@ -580,6 +580,52 @@ int mof_test_amg_vcycle_tables(mof_mesh *mesh, int32_t level, int32_t system, in
  * k_prolong0<1>, <2>, k_prolong0_sa<1>, <2>, k_post3, k_bsweep<false>, <true>,
  * and k_post0_ns<XM, ZH, 2, PK> at 17 + (XM - 1) * 4 + ZH * 2 + PK. */
 int mof_test_vcycle_launches(int64_t *counts);
+/* Test hook: the production inner PCG (pcg<V>() of mof_pcg.hip: its own
+ * launches, grids, chunks and system map) on a given right-hand side, capped
+ * at max_iter iterations. The handle has just solved exactly one batch of B
+ * systems, so the operators are live: precision MOF_PREC_MIXED runs the fp32
+ * solve on A32 (amg != 0: the multigrid of a multigrid solve; amg == 0: the
+ * block-Jacobi D^-1 of a block-Jacobi solve), MOF_PREC_F64 the fp64 one on the
+ * A64 and D^-1 of an fp64 solve. rhs [B][N][2] doubles in the internal order;
+ * rtol, outer_rtol, etol as k_pcg_tol takes them (the per-system scalars it
+ * reads with outer_rtol > 0 are the handle's own, returned in sysd's SD_RR,
+ * SD_FF, SD_EST, SD_XMAX slots); a capped solve fails no system. active ([B]
+ * bytes, or NULL: all): the systems to run -- at most 0.9 B of them and the
+ * launches cover a compacted map. hint (or NULL) = {the first chunk's length,
+ * the bulk hint}, in and out, as pcg() keeps them from batch to batch.
+ * sentinel (or NULL): the word x, r, z, p, q and x0 are filled with
+ * beforehand. The handle's flags and scalars (device and host mirror) are
+ * saved and put back. With cap K the solve ends with the check launch of SpMV
+ * K, so a running system's state is x_K, r_K, z_K, p_K, q_K and the scalars
+ * of step K; K = 0 runs the first-iteration instance alone.
+ * Out, after a stream synchronize, plain copies (any may be NULL): x, r, z, p,
+ * q ([B][N][2] of the working type; z with meta[0] as bf16 pairs, [B][N]
+ * words), x0 ([B][N] words, multigrid only), scal ([2 slots][B][3]: r.z, |r|^2,
+ * p.q -- the partial records of each iteration parity summed by k_red_rzrr /
+ * k_red_pq, the reduction every kernel uses), sysi / sysd ([B][meta[7]] each),
+ * dinv ([B][N][4], block Jacobi only), A ([sell_nb][4]: the operator of
+ * a_system >= 0 as stored). meta[0..8) = bf16 z, symmetric reads, packed index
+ * words, the row kernels reduce the scalars themselves, row blocks per system,
+ * iterations summed over the systems, the slowest system's, the stride of
+ * sysi / sysd. */
+int mof_test_pcg_inner(mof_mesh *mesh, int32_t B, const double *rhs, double rtol, double outer_rtol, double etol,
+                       int32_t amg, uint32_t precision, int32_t max_iter, const uint8_t *active, int32_t *hint,
+                       const uint32_t *sentinel, void *x, void *r, void *z, void *p, void *q, uint32_t *x0,
+                       double *scal, int32_t *sysi, double *sysd, void *dinv, int32_t a_system, void *A,
+                       int32_t *meta);
+/* Test hook: counts[0..23) = launches so far in this process by the
+ * single-domain solver of k_pcg_spmv<V, FIRST, ZH, PK> at (V == double) * 8 +
+ * FIRST * 4 + ZH * 2 + PK (the decomposed solver's count here too), then of
+ * k_red_pq, k_red_rzrr, k_pcg_update, k_pcg_conv_early, k_outer_update and
+ * k_outer_check, and the times pcg() switched its launches to a compacted
+ * system map (at the start of a solve, or for a tail chunk). */
+int mof_test_pcg_launches(int64_t *counts);
+/* Test hook: plain copies, after a stream synchronize, of what the handle's
+ * last solve of a batch of B left: x64 and r64 ([B][N][2] doubles), the last
+ * inner solve's x (xin, [B][N][2] of xin_bytes = 4 or 8 bytes each) and the
+ * per-system sysi / sysd rows ([B][12] each). Any output may be NULL. */
+int mof_test_outer_readback(mof_mesh *mesh, int32_t B, double *x64, double *r64, void *xin, int32_t xin_bytes,
+                            int32_t *sysi, double *sysd);
 
 /* Diagnostic (host only): checks that the XCD-aware workgroup order of the
  * row kernels -- nblk row blocks x batch systems, walked in groups of

@@ -2684,6 +2684,7 @@ float amg_set_omega(mof_mesh *m, float omega) {
 }
 
 int32_t amg_levels(const mof_mesh *m) { return m->amg && m->amg->built ? (int32_t)m->amg->lv.size() : 0; }
+int32_t amg_capacity(const mof_mesh *m) { return m->amg && m->amg->built ? m->amg->cap : 0; }
 
 namespace {
 struct DeviceGuard {

@@ -549,6 +549,8 @@ AmgBf16 amg_bf16_targets(mof_mesh *m, int32_t B);
 void amg_destroy(AmgDevice *g);
 
 int32_t amg_levels(const mof_mesh *m);
+// systems the multigrid's per-system storage holds (0 without a built hierarchy)
+int32_t amg_capacity(const mof_mesh *m);
 // set the fine-level smoother damping of m's multigrid cycle; returns the
 // previous value (0 and no change when m has no hierarchy)
 float amg_set_omega(mof_mesh *m, float omega);

@@ -53,6 +53,12 @@ namespace mof {
 thread_local double g_fetch_ms = 0.0;
 thread_local int64_t g_fetch_n = 0;
 
+// launches so far of each inner-PCG kernel instance (mof_test_pcg_launches):
+// k_pcg_spmv<V, FIRST, ZH, PK> at (V == double) * 8 + FIRST * 4 + ZH * 2 + PK, then the rest;
+// kPcCompact: the times pcg() switched its launches to a compacted system map
+enum { kPcRedPq = 16, kPcRedRzrr, kPcUpdate, kPcConvEarly, kPcOuterUpdate, kPcOuterCheck, kPcCompact, kPcKernels };
+std::atomic<int64_t> g_pcg_launches[kPcKernels];
+
 namespace {
 
 // The operator of B systems sharing a mesh.
@@ -750,8 +756,15 @@ auto spmv_kernel(const PcgArgs<V> &a, bool first) -> void (*)(PcgArgs<V>, int32_
     }
     return first ? k_pcg_spmv<V, true, false> : k_pcg_spmv<V, false, false>;
 }
+// its slot in g_pcg_launches
+template <typename V>
+int spmv_slot(const PcgArgs<V> &a, bool first) {
+    const bool f32 = sizeof(V) == 4;
+    return (f32 ? 0 : 8) + (first ? 4 : 0) + (f32 && a.zh ? 2 : 0) + (f32 && a.mat.sell_idx ? 1 : 0);
+}
 template <typename V>
 void launch_spmv(const PcgArgs<V> &a, bool first, dim3, hipStream_t s, int32_t it, int32_t flags) {
+    ++g_pcg_launches[spmv_slot(a, first)];
     spmv_kernel(a, first)<<<spmv_grid(a), spmv_wg<V>(), 0, s>>>(a, it, flags);
 }
 
@@ -1591,6 +1604,7 @@ int64_t pcg(mof_mesh *m, int32_t B, const MatArgs<V> &mat, const V *dinv, const 
         if (n > 0) {
             MOF_HIP(hipMemcpyAsync(m->ws.smap.p, h_map.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
             a.sm = SysMap{m->ws.smap.p, n};
+            ++g_pcg_launches[kPcCompact];
         }
     }
     // a mesh of at most kSelfRedBlk row blocks: the SpMV and the update
@@ -1599,7 +1613,10 @@ int64_t pcg(mof_mesh *m, int32_t B, const MatArgs<V> &mat, const V *dinv, const 
     k_pcg_init<V><<<g, kWG, 0, s>>>(a, rhs);
     k_pcg_tol<V><<<dim3((unsigned)B), kWG, 0, s>>>(a, rtol, outer_rtol, etol);
     if (amg) precond(0);
-    if (!a.selfred) k_red_rzrr<V><<<dim3((unsigned)a.sm.n), kWG, 0, s>>>(a, 0);
+    if (!a.selfred) {
+        ++g_pcg_launches[kPcRedRzrr];
+        k_red_rzrr<V><<<dim3((unsigned)a.sm.n), kWG, 0, s>>>(a, 0);
+    }
     MOF_HIP(hipGetLastError());
     // The first chunk runs as many iterations as the same solve of the
     // previous batch needed (timesteps of one run converge alike), so the
@@ -1628,16 +1645,27 @@ int64_t pcg(mof_mesh *m, int32_t B, const MatArgs<V> &mat, const V *dinv, const 
                 // events stamped by the kernel's own dispatch packet (start
                 // and end of its execution, as rocprof's kernel trace), not
                 // separate marker packets around it
+                ++g_pcg_launches[spmv_slot(a, it == 0)];
                 hipExtLaunchKernelGGL(spmv_kernel(a, it == 0), spmv_grid(a), dim3(spmv_wg<V>()), 0, s, ev[2 * c], ev[2 * c + 1], 0, a, it, 0);
             } else {
                 launch_spmv(a, it == 0, gx, s, it, 0);
             }
             const unsigned nl = (unsigned)a.sm.n;
-            if (!a.selfred) k_red_pq<V><<<dim3(nl), kWG, 0, s>>>(a, it & 1);
+            if (!a.selfred) {
+                ++g_pcg_launches[kPcRedPq];
+                k_red_pq<V><<<dim3(nl), kWG, 0, s>>>(a, it & 1);
+            }
+            ++g_pcg_launches[kPcUpdate];
             k_pcg_update<V><<<dim3(upd_blocks(m->ws.nblk), nl), kWG, 0, s>>>(a, it);
-            if (early) k_pcg_conv_early<V><<<dim3(nl), kWG, 0, s>>>(a, it);
+            if (early) {
+                ++g_pcg_launches[kPcConvEarly];
+                k_pcg_conv_early<V><<<dim3(nl), kWG, 0, s>>>(a, it);
+            }
             if (amg) precond((it + 1) & 1);
-            if (!a.selfred) k_red_rzrr<V><<<dim3(nl), kWG, 0, s>>>(a, (it + 1) & 1);
+            if (!a.selfred) {
+                ++g_pcg_launches[kPcRedRzrr];
+                k_red_rzrr<V><<<dim3(nl), kWG, 0, s>>>(a, (it + 1) & 1);
+            }
         }
         MOF_HIP(hipGetLastError());
         fetch_flags(m, B, s);
@@ -1663,11 +1691,14 @@ int64_t pcg(mof_mesh *m, int32_t B, const MatArgs<V> &mat, const V *dinv, const 
         if (!done && owe_or_run <= kCompactFrac * B) {
             MOF_HIP(hipMemcpyAsync(m->ws.smap.p, h_map.data(), sizeof(int32_t) * owe_or_run, hipMemcpyHostToDevice, s));
             a.sm = SysMap{m->ws.smap.p, owe_or_run};
+            ++g_pcg_launches[kPcCompact];
         }
     }
     if (!done) {
         // one more check launch so SI_CONV records systems converged at max_iter
-        launch_spmv(a, false, gx, s, it, 0);
+        // (it == 0 only with max_iter = 0, the test hook's cap 0: the first instance, which reads
+        // no previous iteration's scalars)
+        launch_spmv(a, it == 0, gx, s, it, 0);
         if (sp.fail_at_max_iter) k_fail_running<<<dim3((unsigned)((B + 63) / 64)), 64, 0, s>>>(B, it, a.sysi);
         MOF_HIP(hipGetLastError());
         fetch_flags(m, B, s);
@@ -2054,6 +2085,7 @@ int64_t solve_batch(mof_mesh *m, int32_t B, const SolveParams &sp, hipStream_t s
             iters += pcg<float>(m, B, make_mat<float>(m, w.A32.p), w.dinv32.p, rhs, sp.inner_rtol, sp, s,
                                 max_iters, tm, &m->iter_hint[(amg ? 16 : 32) + std::min(o, 15)], amg,
                                 o > 0 && sp.adaptive_inner ? sp.rtol : 0.0, sp.etol);
+            ++g_pcg_launches[kPcOuterUpdate];
             k_outer_update<float><<<gv, kWG, 0, s>>>(m->N, o == 0, reinterpret_cast<float *>(w.vx.p),
                                                     w.sysi.p, w.x64.p, rdx, B, w.part_dx.p);
         } else {
@@ -2061,12 +2093,14 @@ int64_t solve_batch(mof_mesh *m, int32_t B, const SolveParams &sp, hipStream_t s
                                  o == 0 ? 0.5 * sp.rtol : sp.inner_rtol, sp, s, max_iters, tm,
                                  &m->iter_hint[std::min(o, 15)], false, o > 0 && sp.adaptive_inner ? sp.rtol : 0.0,
                                  sp.etol);
+            ++g_pcg_launches[kPcOuterUpdate];
             k_outer_update<double><<<gv, kWG, 0, s>>>(m->N, o == 0, w.vx.p, w.sysi.p, w.x64.p, rdx, B,
                                                      w.part_dx.p);
         }
         const RedArgs rd{1, 0, w.nblk, m->N};
         launch_residual(m, w.nblk, B, s, rd, w.rhs.p, w.x64.p, w.sysi.p,
                                                               w.r64.p, w.part_rr0.p);
+        ++g_pcg_launches[kPcOuterCheck];
         k_outer_check<<<dim3((unsigned)B), kWG, 0, s>>>(rd, B, w.part_rr0.p, rdx, w.part_dx.p, o == 0, sp.rtol,
                                                         sp.etol, w.sysd.p, w.sysi.p);
         MOF_HIP(hipGetLastError());
@@ -2382,4 +2416,224 @@ bool xcd_map_covers(int32_t nblk, int32_t B, int32_t grp) {
     return true;
 }
 
+namespace {
+
+struct PcgDeviceGuard {
+    int prev = 0;
+    explicit PcgDeviceGuard(int d) {
+        (void)hipGetDevice(&prev);
+        MOF_HIP(hipSetDevice(d));
+    }
+    ~PcgDeviceGuard() { (void)hipSetDevice(prev); }
+};
+
+// the handle's per-system flags and scalars (device and host mirror) replaced
+// for one test solve and put back
+struct SysSwap {
+    mof_mesh *m;
+    int32_t B;
+    std::vector<int32_t> si;
+    std::vector<double> sd;
+    std::vector<int32_t> hsi;
+    std::vector<double> hsd;
+    SysSwap(mof_mesh *mm, int32_t b, const uint8_t *active)
+        : m(mm), B(b), si((size_t)b * kSysStride), sd((size_t)b * kSysStride) {
+        Workspace &w = m->ws;
+        MOF_HIP(hipMemcpy(si.data(), w.sysi.p, si.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        MOF_HIP(hipMemcpy(sd.data(), w.sysd.p, sd.size() * sizeof(double), hipMemcpyDeviceToHost));
+        hsi.assign(m->h_sysi, m->h_sysi + si.size());
+        hsd.assign(m->h_sysd, m->h_sysd + sd.size());
+        std::vector<int32_t> now(si.size(), 0);
+        for (int32_t k = 0; k < B; ++k) {
+            now[(size_t)k * kSysStride + SI_CONV] = -1;
+            now[(size_t)k * kSysStride + SI_ACTIVE] = !active || active[k];
+        }
+        std::copy(now.begin(), now.end(), m->h_sysi);  // pcg() reads the mirror for the systems to run
+        MOF_HIP(hipMemcpy(w.sysi.p, now.data(), now.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    ~SysSwap() {
+        Workspace &w = m->ws;
+        (void)hipMemcpy(w.sysi.p, si.data(), si.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+        (void)hipMemcpy(w.sysd.p, sd.data(), sd.size() * sizeof(double), hipMemcpyHostToDevice);
+        std::copy(hsi.begin(), hsi.end(), m->h_sysi);
+        std::copy(hsd.begin(), hsd.end(), m->h_sysd);
+    }
+};
+
+// mof_test_pcg_inner for one working type
+template <typename V>
+void test_pcg_inner(mof_mesh *m, int32_t B, const double *rhs, double rtol, double outer_rtol, double etol, bool amg,
+                    int32_t max_iter, const uint8_t *active, int32_t *hint2, const uint32_t *sentinel, void *x,
+                    void *r, void *z, void *p, void *q, uint32_t *x0, double *scal, int32_t *sysi, double *sysd,
+                    void *dinv, int32_t a_system, void *A, int32_t *meta) {
+    constexpr bool f32 = sizeof(V) == 4;
+    Workspace &w = m->ws;
+    const size_t N = (size_t)m->N, nv = N * B, snb = (size_t)m->pat.sell_nb();
+    MOF_REQUIRE(B >= 1 && B <= w.cap && w.nblk > 0, "the handle's last batch had fewer systems");
+    MOF_REQUIRE(m->n_own == m->N, "a decomposed part's handle");
+    MOF_REQUIRE(max_iter >= 0, "negative iteration cap");
+    MOF_REQUIRE(!amg || f32, "the multigrid preconditions the fp32 inner solve only");
+    const V *Ap;
+    const V *dv;
+    if constexpr (f32) {
+        MOF_REQUIRE(w.A32.n >= 4 * snb * B, "no fp32 operator: the last solve was not mixed-precision");
+        Ap = w.A32.p;
+        dv = w.dinv32.p;
+    } else {
+        MOF_REQUIRE(w.A64.n >= 4 * snb * B, "no fp64 operator: the last solve was not an fp64 one");
+        Ap = w.A64.p;
+        dv = w.dinv64.p;
+    }
+    if (amg) {
+        MOF_REQUIRE(m->amg && amg_levels(m) >= 2, "the handle has no built multigrid");
+        MOF_REQUIRE(B <= amg_capacity(m), "the multigrid's storage holds fewer systems");
+    }
+    MOF_REQUIRE(a_system < B, "bad system to read back");
+    hipStream_t s = m->stream;
+    MOF_HIP(hipStreamSynchronize(s));
+    DevArray<double> drhs;
+    drhs.alloc(2 * nv);
+    MOF_HIP(hipMemcpy(drhs.p, rhs, sizeof(double) * 2 * nv, hipMemcpyHostToDevice));
+    SysSwap swap(m, B, active);
+    float *x0p = amg ? amg_fine(m).x0 : nullptr;
+    if (sentinel) {
+        for (DevArray<double> *a : {&w.vx, &w.vr, &w.vz, &w.vp, &w.vq})
+            MOF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a->p), (int)*sentinel,
+                                      2 * nv * sizeof(V) / 4, s));
+        if (x0p) MOF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(x0p), (int)*sentinel, nv, s));
+    }
+    // partial records of systems that never run read as zero
+    MOF_HIP(hipMemsetAsync(w.part_pq.p, 0, sizeof(double) * 2 * w.nblk * B, s));
+    MOF_HIP(hipMemsetAsync(w.part_rzrr.p, 0, sizeof(double) * 4 * w.nblk * B, s));
+    MOF_HIP(hipMemsetAsync(w.sc.p, 0, sizeof(double) * 6 * B, s));
+    SolveParams sp{};
+    sp.precision = f32 ? MOF_PREC_MIXED : MOF_PREC_F64;
+    sp.block_jacobi = true;
+    sp.time_spmv = false;
+    sp.amg = amg;
+    sp.max_iter = max_iter;
+    sp.max_outer = 1;
+    sp.rtol = rtol;
+    sp.inner_rtol = rtol;
+    sp.etol = etol;
+    sp.stall = amg ? kPcgStall : 0;
+    sp.fail_at_max_iter = false;
+    std::vector<int32_t> hint(2 * kBulkHint, 0);
+    if (hint2) {
+        hint[0] = hint2[0];
+        hint[kBulkHint] = hint2[1];
+    }
+    int32_t max_iters = 0;
+    const MatArgs<V> mat = make_mat<V>(m, Ap);
+    const int64_t total = pcg<V>(m, B, mat, dv, drhs.p, rtol, sp, s, &max_iters, nullptr, hint.data(), amg,
+                                 outer_rtol, etol);
+    // both slots' scalars as the kernels form them: k_red_rzrr's and k_red_pq's reduction (reduce_sys)
+    // of the partial records the solve left, for every system
+    PcgArgs<V> a = make_args<V>(m, B, mat, dv);
+    for (int32_t slot = 0; slot < 2; ++slot) {
+        k_red_rzrr<V><<<dim3((unsigned)B), kWG, 0, s>>>(a, slot);
+        k_red_pq<V><<<dim3((unsigned)B), kWG, 0, s>>>(a, slot);
+    }
+    MOF_HIP(hipGetLastError());
+    MOF_HIP(hipStreamSynchronize(s));
+    auto get = [&](void *dst, const void *src, size_t bytes) {
+        if (dst) MOF_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    };
+    const bool zh = f32 && amg && amg_fine(m).regular;
+    get(x, w.vx.p, sizeof(V) * 2 * nv);
+    get(r, w.vr.p, sizeof(V) * 2 * nv);
+    get(z, w.vz.p, zh ? sizeof(uint32_t) * nv : sizeof(V) * 2 * nv);
+    get(p, w.vp.p, sizeof(V) * 2 * nv);
+    get(q, w.vq.p, sizeof(V) * 2 * nv);
+    if (x0p) get(x0, x0p, sizeof(uint32_t) * nv);
+    if (scal) {
+        std::vector<double> sc((size_t)6 * B);
+        get(sc.data(), w.sc.p, sizeof(double) * 6 * B);
+        for (int32_t slot = 0; slot < 2; ++slot)
+            for (int32_t b = 0; b < B; ++b) {
+                double *o = scal + 3 * ((size_t)slot * B + b);
+                o[0] = sc[2 * ((size_t)slot * B + b)];
+                o[1] = sc[2 * ((size_t)slot * B + b) + 1];
+                o[2] = sc[(size_t)4 * B + (size_t)slot * B + b];
+            }
+    }
+    get(sysi, w.sysi.p, sizeof(int32_t) * kSysStride * B);
+    get(sysd, w.sysd.p, sizeof(double) * kSysStride * B);
+    if (!amg) get(dinv, dv, sizeof(V) * 4 * nv);
+    if (a_system >= 0) get(A, Ap + 4 * snb * (size_t)a_system, sizeof(V) * 4 * snb);
+    if (hint2) {
+        hint2[0] = hint[0];
+        hint2[1] = hint[kBulkHint];
+    }
+    if (meta) {
+        const int32_t v[8] = {zh,
+                              m->sym_reads,
+                              mat.sell_idx != nullptr,
+                              w.nblk <= kSelfRedBlk,
+                              w.nblk,
+                              (int32_t)std::min<int64_t>(total, INT32_MAX),
+                              max_iters,
+                              kSysStride};
+        std::copy(v, v + 8, meta);
+    }
+}
+
+}  // namespace
+
 }  // namespace mof
+
+// ---- test hooks (include/mof.h) ------------------------------------------------
+
+int mof_io_guard(const std::function<void()> &f);  // mof_abi.cpp: status + mof_last_error
+
+extern "C" {
+
+int mof_test_pcg_inner(mof_mesh *m, int32_t B, const double *rhs, double rtol, double outer_rtol, double etol,
+                       int32_t amg, uint32_t precision, int32_t max_iter, const uint8_t *active, int32_t *hint,
+                       const uint32_t *sentinel, void *x, void *r, void *z, void *p, void *q, uint32_t *x0,
+                       double *scal, int32_t *sysi, double *sysd, void *dinv, int32_t a_system, void *A,
+                       int32_t *meta) {
+    return mof_io_guard([&] {
+        MOF_REQUIRE(m && rhs, "NULL argument");
+        MOF_REQUIRE(precision == MOF_PREC_MIXED || precision == MOF_PREC_F64, "bad precision");
+        mof::mesh_join_prep(m);
+        mof::PcgDeviceGuard dg(m->device);
+        if (precision == MOF_PREC_MIXED)
+            mof::test_pcg_inner<float>(m, B, rhs, rtol, outer_rtol, etol, amg != 0, max_iter, active, hint, sentinel, x,
+                                       r, z, p, q, x0, scal, sysi, sysd, dinv, a_system, A, meta);
+        else
+            mof::test_pcg_inner<double>(m, B, rhs, rtol, outer_rtol, etol, amg != 0, max_iter, active, hint, sentinel,
+                                        x, r, z, p, q, x0, scal, sysi, sysd, dinv, a_system, A, meta);
+    });
+}
+
+int mof_test_pcg_launches(int64_t *counts) {
+    return mof_io_guard([&] {
+        MOF_REQUIRE(counts, "NULL argument");
+        for (int k = 0; k < mof::kPcKernels; ++k) counts[k] = mof::g_pcg_launches[k].load();
+    });
+}
+
+int mof_test_outer_readback(mof_mesh *m, int32_t B, double *x64, double *r64, void *xin, int32_t xin_bytes,
+                            int32_t *sysi, double *sysd) {
+    return mof_io_guard([&] {
+        MOF_REQUIRE(m, "mesh is NULL");
+        mof::mesh_join_prep(m);
+        mof::Workspace &w = m->ws;
+        MOF_REQUIRE(B >= 1 && B <= w.cap, "the handle's last batch had fewer systems");
+        MOF_REQUIRE(!xin || xin_bytes == 4 || xin_bytes == 8, "the inner x holds floats or doubles");
+        mof::PcgDeviceGuard dg(m->device);
+        MOF_HIP(hipStreamSynchronize(m->stream));
+        const size_t nv = (size_t)m->N * B;
+        auto get = [&](void *dst, const void *src, size_t bytes) {
+            if (dst) MOF_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+        };
+        get(x64, w.x64.p, sizeof(double) * 2 * nv);
+        get(r64, w.r64.p, sizeof(double) * 2 * nv);
+        get(xin, w.vx.p, (size_t)xin_bytes * 2 * nv);
+        get(sysi, w.sysi.p, sizeof(int32_t) * mof::kSysStride * B);
+        get(sysd, w.sysd.p, sizeof(double) * mof::kSysStride * B);
+    });
+}
+
+}  // extern "C"

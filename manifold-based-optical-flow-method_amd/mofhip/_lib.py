@@ -66,6 +66,7 @@ EXPORTS = (
     "mof_test_winding_pass", "mof_winding_timing", "mof_closest_vertices",
     "mof_test_amg_levels", "mof_test_amg_readback", "mof_test_force_galerkin_ns", "mof_test_galerkin_launches",
     "mof_test_amg_vcycle", "mof_test_amg_vcycle_tables", "mof_test_vcycle_launches",
+    "mof_test_pcg_inner", "mof_test_pcg_launches", "mof_test_outer_readback",
 )
 
 
@@ -221,6 +222,9 @@ def lib():
             "mof_test_amg_vcycle": ([P, i32, P, P, i32, P, i32, i32, P, P, P, i32, P, P, P, P, P], ctypes.c_int),
             "mof_test_amg_vcycle_tables": ([P, i32, i32] + [P] * 9, ctypes.c_int),
             "mof_test_vcycle_launches": ([P], ctypes.c_int),
+            "mof_test_pcg_inner": ([P, i32, P, f64, f64, f64, i32, u32, i32] + [P] * 13 + [i32, P, P], ctypes.c_int),
+            "mof_test_pcg_launches": ([P], ctypes.c_int),
+            "mof_test_outer_readback": ([P, i32, P, P, P, i32, P, P], ctypes.c_int),
             "mof_xcd_map_check": ([i32, i32, i32], ctypes.c_int),
             "mof_xcd_batch_cap": ([i64, i32, P], ctypes.c_int),
             "mof_singularities_compact": ([i32, P, P, i32, i32, P, i32, f64, u32, P, i64, P, P, P, P, P,

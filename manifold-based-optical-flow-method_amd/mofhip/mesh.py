@@ -637,3 +637,100 @@ def amg_vcycle(mesh: "DeviceMesh", r, level_sizes, systems=(), smap=None, retire
               for t in range(4)] if tap else []
         out["sys"][int(s)] = {"r1": r1[k].copy(), "taps": tp, "coarse": lev}
     return out
+
+
+PCG_KERNELS = tuple("spmv_%s%s%s%s" % (v, "_first" if first else "", "_zh" if zh else "", "_pk" if pk else "")
+                    for v in ("f32", "f64") for first in (0, 1) for zh in (0, 1) for pk in (0, 1)) + (
+    "red_pq", "red_rzrr", "update", "conv_early", "outer_update", "outer_check", "compact")
+SYS_I = ("CONV", "ACTIVE", "FAILED", "ITSUM", "BEST_IT", "FAIL_IT", "FAIL_WHY", "ITMAX", "MET")
+SYS_D = ("TOL2", "RR", "FF", "REL", "RR0", "BEST", "OUTER", "EST", "XMAX")
+SYS_STRIDE = 12
+
+
+def pcg_launches() -> dict:
+    """Tests only (mof_test_pcg_launches): launches so far in this process of
+    each inner-PCG kernel instance (``PCG_KERNELS``; ``spmv_<f32|f64>[_first][_zh][_pk]``
+    are k_pcg_spmv's; the f64 ones exist without ``_zh`` / ``_pk`` only; ``compact``:
+    the times pcg() switched to a compacted system map)."""
+    c = np.zeros(len(PCG_KERNELS), dtype=np.int64)
+    L.check(L.lib().mof_test_pcg_launches(L.ptr(c)))
+    return {k: int(v) for k, v in zip(PCG_KERNELS, c)}
+
+
+def _sys_rows(si, sd):
+    out = {k: si[:, i].copy() for i, k in enumerate(SYS_I)}
+    out.update({k: sd[:, i].copy() for i, k in enumerate(SYS_D)})
+    return out
+
+
+def pcg_inner(mesh: "DeviceMesh", rhs, rtol, cap, precond="jacobi", precision="mixed", outer_rtol=0.0, etol=0.0,
+              active=None, hint=None, sentinel=None, a_system=-1, device=None) -> dict:
+    """Tests only (mof_test_pcg_inner): the production inner PCG of the
+    handle's last batch on ``rhs`` (B, N, 2) float64 in the internal order,
+    capped at ``cap`` iterations. ``active`` (B,) selects the systems to run,
+    ``hint`` = (first chunk, bulk hint) as pcg() keeps them, ``sentinel`` the
+    word the vectors are filled with beforehand. Returns the vectors ``x, r, p,
+    q`` (B, N, 2) in the working type, ``z`` (B, N, 2) decoded and ``z_words``,
+    ``x0_words`` (B, N) with the multigrid, ``scal`` (2 slots, B, 3: r.z, |r|^2,
+    p.q), ``sys`` (the sysi / sysd rows by name), ``dinv`` (B, N, 2, 2) with
+    block Jacobi, ``A`` (sell_blocks, 2, 2) of ``a_system``, ``hint`` after the
+    solve and ``zh, sym, packed, selfred, nblk, iterations, slowest``."""
+    rhs = np.ascontiguousarray(rhs, dtype=np.float64)
+    B, N = rhs.shape[0], rhs.shape[1]
+    assert rhs.shape == (B, N, 2) and N == mesh.N
+    amg = {"jacobi": 0, "amg": 1}[precond]
+    dt = {"mixed": np.float32, "f64": np.float64}[precision]
+    wt = {"mixed": np.uint32, "f64": np.uint64}[precision]
+    vec = {k: np.zeros((B, N, 2), dtype=wt) for k in "xrzpq"}
+    x0 = np.zeros((B, N), dtype=np.uint32)
+    scal = np.zeros((2, B, 3), dtype=np.float64)
+    si = np.zeros((B, SYS_STRIDE), dtype=np.int32)
+    sd = np.zeros((B, SYS_STRIDE), dtype=np.float64)
+    dinv = np.zeros((B, N, 2, 2), dtype=dt)
+    nb = int(mesh.info(device)["sell_blocks"])
+    A = np.zeros((nb, 2, 2), dtype=dt)
+    meta = np.zeros(8, dtype=np.int32)
+    act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
+    assert act is None or act.shape == (B,)
+    hn = np.zeros(2, dtype=np.int32) if hint is None else np.ascontiguousarray(hint, dtype=np.int32).copy()
+    sw = None if sentinel is None else np.array([sentinel], dtype=np.uint32)
+    o = lambda a: None if a is None else L.ptr(a)  # noqa: E731
+    with mesh.lock(device):
+        L.check(L.lib().mof_test_pcg_inner(
+            mesh.handle(device), B, L.ptr(rhs), float(rtol), float(outer_rtol), float(etol), amg,
+            {"mixed": L.MOF_PREC_MIXED, "f64": L.MOF_PREC_F64}[precision], int(cap), o(act), L.ptr(hn), o(sw),
+            L.ptr(vec["x"]), L.ptr(vec["r"]), L.ptr(vec["z"]), L.ptr(vec["p"]), L.ptr(vec["q"]), L.ptr(x0),
+            L.ptr(scal), L.ptr(si), L.ptr(sd), L.ptr(dinv), int(a_system), L.ptr(A), L.ptr(meta)))
+    assert meta[7] == SYS_STRIDE
+    out = {k: vec[k].view(dt) for k in "xrpq"}
+    out["words"] = vec
+    zh = bool(meta[0])
+    if zh:
+        w = vec["z"].reshape(-1)[:B * N].reshape(B, N).copy()
+        out["z_words"] = w
+        out["z"] = np.stack([(w << np.uint32(16)).view(np.float32), (w & np.uint32(0xFFFF0000)).view(np.float32)], axis=-1)
+    else:
+        out["z_words"] = vec["z"]
+        out["z"] = vec["z"].view(dt)
+    out.update(x0_words=x0 if amg else None, scal=scal, sys=_sys_rows(si, sd), dinv=None if amg else dinv,
+               A=A if a_system >= 0 else None, hint=(int(hn[0]), int(hn[1])), zh=zh, sym=bool(meta[1]),
+               packed=bool(meta[2]), selfred=bool(meta[3]), nblk=int(meta[4]), iterations=int(meta[5]),
+               slowest=int(meta[6]))
+    return out
+
+
+def outer_readback(mesh: "DeviceMesh", B: int, precision="mixed", device=None) -> dict:
+    """Tests only (mof_test_outer_readback): what the handle's last solve of a
+    batch of ``B`` left -- ``x64``, ``r64`` (B, N, 2), the last inner solve's x
+    ``xin`` (B, N, 2) in the working type of ``precision`` and ``sys`` (the
+    sysi / sysd rows by name)."""
+    N = mesh.N
+    x64 = np.zeros((B, N, 2))
+    r64 = np.zeros((B, N, 2))
+    xin = np.zeros((B, N, 2), dtype={"mixed": np.float32, "f64": np.float64}[precision])
+    si = np.zeros((B, SYS_STRIDE), dtype=np.int32)
+    sd = np.zeros((B, SYS_STRIDE), dtype=np.float64)
+    with mesh.lock(device):
+        L.check(L.lib().mof_test_outer_readback(mesh.handle(device), int(B), L.ptr(x64), L.ptr(r64), L.ptr(xin),
+                                                xin.itemsize, L.ptr(si), L.ptr(sd)))
+    return {"x64": x64, "r64": r64, "xin": xin, "sys": _sys_rows(si, sd)}
