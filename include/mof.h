@@ -800,6 +800,51 @@ int mof_winding_timing(double *ms);
 int mof_closest_vertices(mof_mesh *mesh, const double *points, int32_t Q, uint32_t flags, void *stream,
                          int32_t *vertex);
 
+/* ---- the spatiotemporal modes of the reference's two
+ * S4_spatiotemporal_decomposition_* scripts, by the method of snapshots ------
+ * The scripts take np.linalg.svd of X = V1 + i V2 (K x N complex;
+ * MOF_MODES_COMPLEX) or of [V1 | V2] (K x 2N real), V1 = V[:, :N],
+ * V2 = V[:, N:] of the planar fields V (K, 2N). With K << N the left vectors
+ * and singular values are those of the K x K Gram matrix, whose eigenproblem
+ * is the caller's (mofhip/modes.py: numpy's eigh; the library links no LAPACK):
+ *   mof_modes_gram: S (K, K) = V V^T over all 2N columns, exactly symmetric;
+ *     with MOF_MODES_COMPLEX also A (K, K) = V2 V1^T - V1 V2^T, exactly
+ *     antisymmetric with a zero diagonal (X X^H = S + i A; the concat Gram
+ *     matrix is S alone; A may be NULL without the flag). The N columns are
+ *     summed in chunks of a fixed library constant length (2048) on the fp64
+ *     matrix cores, and the chunks in ascending order, without atomics: the
+ *     result is the same from run to run and for any pass size.
+ *   mof_modes_project: for the first r <= K eigenvectors W = P + i Q (P, Q
+ *     (K, r) row-major; Q unused and may be NULL without MOF_MODES_COMPLEX),
+ *     Y (r, 2N) = W^H X in V's planar layout: Y[:, :N] = P^T V1 + Q^T V2,
+ *     Y[:, N:] = P^T V2 - Q^T V1; without the flag Y = P^T V over the 2N
+ *     columns. Each entry is one fused-multiply-add chain over the K rows in
+ *     ascending order. sigma_r (r, may be NULL): the row norms |Y_j|, summed in
+ *     a fixed order. Y_j is the scripts' sigma * vt; mof_velocity_vectors(e, Y,
+ *     N, r, ...) turns it into their 3-D mode vectors.
+ * V is taken in bounded passes (columns for the Gram matrix, rows for the
+ * projection), so the device workspace stays bounded; host pointers, or device
+ * pointers on `device` with MOF_IO_DEVICE (stream: hipStream_t or NULL).
+ * MOF_E_ARG for K < 1, N < 1, r > K, N > 2^29 (column indices are 32-bit) or
+ * K > 8192 (the K x K step is meant to be small: S and A take 512 MiB each
+ * there). Accuracy: the Gram matrix carries
+ * an error of about 4 K N u |G|, so sigma_j is good to that over sigma_j
+ * relative to sigma_1^2 -- modes below about 1e-6 sigma_1 are not resolved. */
+#define MOF_MODES_COMPLEX 2048u /* mof_modes_gram / mof_modes_project: the
+                                    complex K x N matrix V1 + i V2 */
+int mof_modes_gram(int32_t device, const double *V, int32_t K, int32_t N, uint32_t flags, void *stream, double *S,
+                   double *A);
+int mof_modes_project(int32_t device, const double *V, int32_t K, int32_t N, const double *P, const double *Q,
+                      int32_t r, uint32_t flags, void *stream, double *Y, double *sigma_r);
+/* Tests only: columns per chunk of mof_modes_gram (rounded up to a multiple
+ * of 16; 0: the library's constant) -- this one changes the summation order. */
+int mof_test_modes_chunk(int32_t cols);
+/* Tests only: both calls stage at most rows * 2N values of V per pass (the
+ * projection `rows` rows, the Gram matrix as many chunks of its K rows as
+ * that holds, at least one; 0: the library's choice). The results do not
+ * depend on it. */
+int mof_test_modes_pass(int32_t rows);
+
 /* Measurement helper for bench.py: launches the PCG SpMV kernel `reps` times
  * back to back on `batch` systems of the last solve's working set, timed with
  * HIP events on the handle's stream. Returns the mean launch time and the

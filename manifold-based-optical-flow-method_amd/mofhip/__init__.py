@@ -17,3 +17,5 @@ from .streamline import (streamline_map, streamline_map_device, streamline_lists
                          track_static_vectorfields_over_time, extract_static_streamline_dot_product)
 from .winding import (winding_map, winding_map_device, winding_levels, winding_levels_device,  # noqa: F401
                       winding_rings, closest_vertices, calculate_winding_numbers, winding_lines)
+from .modes import (velocity_modes, velocity_modes_device, spatiotemporal_modes, modes_gram,  # noqa: F401
+                    modes_project, process_V_k_to_complex, calculate_V_k_from_complex, calculate_percentages)

@@ -44,6 +44,7 @@ MOF_COORDS_F32 = 32
 MOF_DD_STAGED = 64
 MOF_WAVE_PHASE = 512
 MOF_WIND_ALL_LEVELS = 1024
+MOF_MODES_COMPLEX = 2048
 MOF_CSR_A2 = 0
 MOF_CSR_A_LAST = 1
 
@@ -67,6 +68,7 @@ EXPORTS = (
     "mof_test_amg_levels", "mof_test_amg_readback", "mof_test_force_galerkin_ns", "mof_test_galerkin_launches",
     "mof_test_amg_vcycle", "mof_test_amg_vcycle_tables", "mof_test_vcycle_launches",
     "mof_test_pcg_inner", "mof_test_pcg_launches", "mof_test_outer_readback",
+    "mof_modes_gram", "mof_modes_project", "mof_test_modes_chunk", "mof_test_modes_pass",
 )
 
 
@@ -201,6 +203,10 @@ def lib():
             "mof_test_winding_pass": ([i32], ctypes.c_int),
             "mof_winding_timing": ([P], ctypes.c_int),
             "mof_closest_vertices": ([P, P, i32, u32, P, P], ctypes.c_int),
+            "mof_modes_gram": ([i32, P, i32, i32, u32, P, P, P], ctypes.c_int),
+            "mof_modes_project": ([i32, P, i32, i32, P, P, i32, u32, P, P, P], ctypes.c_int),
+            "mof_test_modes_chunk": ([i32], ctypes.c_int),
+            "mof_test_modes_pass": ([i32], ctypes.c_int),
             "mof_singularities": ([i32, P, P, i32, i32, P, i32, f64, u32, P, P, P, P, P],
                                   ctypes.c_int),
             "mof_amg_probe": ([P, P, i32, i32, P, P, P, P], ctypes.c_int),
