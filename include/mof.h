@@ -557,7 +557,9 @@ int mof_test_galerkin_launches(int64_t *counts);
  * level >= 1 its b, x, r, y, [n][4] floats each, r at the member positions).
  * meta[0..4) = zh in force, xm (level 0's corrected iterate: 1 bf16 in place,
  * 2 float2), the first level of the fused k_subcycle, row blocks per system.
- * Any output but z may be NULL. */
+ * Any output but z may be NULL. On a decomposed part's handle
+ * (mof_dd_test_part) the cycle runs as pcg_dd calls it: zh = -1 means float2,
+ * and rz sums the records of the owned rows alone. */
 int mof_test_amg_vcycle(mof_mesh *mesh, int32_t B, const float *r, const int32_t *smap, int32_t nl,
                         const uint8_t *retired, int32_t zh, int32_t tap, const uint32_t *sentinel, uint32_t *z,
                         double *rz, int32_t nsys, const int32_t *systems, uint32_t *r1, uint32_t *taps,
@@ -725,6 +727,81 @@ int mof_dd_get_info(const mof_dd *dd, mof_dd_info *info);
  * workspace allocation reports a failure on rank `rank` of this handle's
  * solves (-1: off) -- exercises the ranks' agreement on a failed recovery. */
 int mof_dd_test_fail_recovery_alloc(mof_dd *dd, int32_t rank);
+/* Test hook (no device launch): local part l of the handle (0 <=
+ * l < local_parts) and its halo plan. *mesh: the part's own mof_mesh, borrowed
+ * (it lives and dies with dd; never destroy it) -- its rows are the part's
+ * n_own owned vertices, then its n_ghost ghosts, in the order l2g gives, and
+ * the read-only hooks (mof_test_assembly_readback, mof_test_amg_levels,
+ * mof_test_amg_readback, mof_test_amg_vcycle_tables, mof_test_outer_readback)
+ * take it after a solve of dd. Every array is optional: call once with them
+ * NULL for sizes[0..12) =
+ *   0 the part's id   1 n_own   2 n_ghost   3 neighbour parts   4 rows sent per
+ *   exchange   5 local triangles   6 P   7 local parts of the handle   8 entries
+ *   of the in-process halo gather (ghost rows of all parts; 0 on a rank's
+ *   handle)   9 cap (systems the shared records and staging buffers hold)
+ *   10 nmax (row blocks of the largest part: the shared records' stride; 0
+ *   before the first solve)   11 the staged gather's record stride (rows).
+ * l2g (n_own + n_ghost): local row -> caller vertex. ghost_owner, ghost_src
+ * (n_ghost each): the part that owns ghost g and its local row there. nbr
+ * (neighbours, ascending), recv_off (neighbours + 1; 1 entry, 0, without a
+ * neighbour): ghosts [recv_off[k], recv_off[k + 1]) come from nbr[k]. send_off
+ * (neighbours + 1), send_idx (rows sent): the owned rows nbr[k] reads, in the
+ * order of its ghost rows; packed for an exchange of B systems as [B][rows of
+ * the segment][2] at element offset 2 B send_off[k] of the part's region. */
+int mof_dd_test_part(mof_dd *dd, int32_t l, mof_mesh **mesh, int64_t *sizes, int32_t *l2g, int32_t *ghost_owner,
+                     int32_t *ghost_src, int32_t *nbr, int32_t *recv_off, int32_t *send_off, int32_t *send_idx);
+/* Test hook: the production halo exchange (dd_halo: its own launches, tables
+ * and, with MOF_DD_STAGED, staging buffers and segment offsets) on given
+ * vectors. The in-process handle has solved a batch of at least B systems, so
+ * the workspaces exist. in: one vector per local part, concatenated in part
+ * order, each [B][n_own + n_ghost][2] with the ghost rows included -- floats
+ * (f32 != 0) or doubles into the inner solver's z (which = 0), doubles into
+ * x64 (which = 1). out, same layout: every part's vector after the exchange.
+ * sentinel (or NULL): the word both staging buffers are filled with
+ * beforehand. The parts' own z / x64 are saved and put back. */
+int mof_dd_test_halo(mof_dd *dd, int32_t B, int32_t which, int32_t f32, const void *in, void *out,
+                     const uint32_t *sentinel);
+/* Test hook: the production gather of V (dd_gather_v: one scatter per part,
+ * or with MOF_DD_STAGED the owned-row records and their one scatter) from
+ * given x64 (as mof_dd_test_halo's `in`, doubles) and given per-system failed
+ * flags ([B] bytes, or NULL: the handle's own). prefill (or NULL): the 64-bit
+ * word V -- and the staged path's records -- hold beforehand. V: [B][2 N]
+ * doubles, planar, caller order. The parts' x64 and flags are saved and put
+ * back. */
+int mof_dd_test_gather(mof_dd *dd, int32_t B, const double *x64, const uint8_t *failed, const uint64_t *prefill,
+                       double *V);
+/* Test hook: mof_test_pcg_inner for the decomposed driver (pcg_dd<V>() of
+ * mof_pcg.hip: its own launches, halo exchanges, record all-gathers and
+ * chunks) on a given right-hand side per local part, capped at max_iter
+ * iterations; a capped solve fails no system. The in-process handle has just
+ * solved exactly one batch of B systems with the preconditioner and precision
+ * asked for (amg, precision as mof_test_pcg_inner). rhs: one [B][n_own +
+ * n_ghost][2] array of doubles per part, concatenated in part order, local row
+ * order (the ghost rows are never read). sentinel (or NULL): the word every
+ * part's x, r, z, p, q and x0 are filled with beforehand. Every part's rhs,
+ * flags and scalars (device and host mirror) are saved and put back. With cap
+ * K the solve ends with the check launch of SpMV K (K = 0: the
+ * first-iteration instance alone), as mof_test_pcg_inner.
+ * Out, plain copies after a stream synchronize (any may be NULL), per-part
+ * arrays concatenated in part order: x, r, z, p, q ([B][n_loc][2] of the
+ * working type; z is float2 on every part), sysi / sysd ([B][meta[4]] per
+ * part), dinv ([B][n_loc][4], block Jacobi only), A ([sell_nb][4]: the
+ * operator of a_system >= 0 as each part stores it). part_rzrr ([2 slots][P][B]
+ * [nmax][2]: r.z, |r|^2) and part_pq ([2 slots][P][B][nmax]): the shared partial
+ * records as the solve left them, nmax = meta[0] the row blocks of the largest
+ * part. scal ([2 slots][B][3]: r.z, |r|^2, p.q): each slot's records summed by
+ * k_red_rzrr / k_red_pq with part 0's arguments. meta[0..6) = nmax, P,
+ * iterations summed over the systems, the slowest system's, the stride of
+ * sysi / sysd, local parts. */
+int mof_dd_test_pcg_inner(mof_dd *dd, int32_t B, const double *rhs, double rtol, int32_t amg, uint32_t precision,
+                          int32_t max_iter, const uint32_t *sentinel, void *x, void *r, void *z, void *p, void *q,
+                          int32_t *sysi, double *sysd, void *dinv, int32_t a_system, void *A, double *part_rzrr,
+                          double *part_pq, double *scal, int32_t *meta);
+/* Test hook: counts[0..9) = launches so far in this process of
+ * k_halo_pull<float>, <double>, k_halo_pack<float>, <double>,
+ * k_halo_unpack<float>, <double>, k_dd_scatter, k_dd_own_pack and
+ * k_dd_own_scatter. */
+int mof_dd_test_launches(int64_t *counts);
 
 /* mof_solve_range on the decomposed system (same arguments and results; with
  * RCCL every rank passes the same k-range and receives the whole V). */

@@ -2097,7 +2097,9 @@ bool amg_build(mof_mesh *m) {
         d.alloc(h.size());
         if (!h.empty()) d.upload(h.data(), h.size(), s);
     };
-    if (!m->sym_reads && m->n_own == m->N) put_i(G.mir0, H.mirror);  // k_h0_twins
+    // k_h0_twins; a decomposed part's table (built with nown) names a twin for its owned-owned
+    // lower blocks alone, so the ghost rows and columns keep their identity / zero blocks
+    if (!m->sym_reads) put_i(G.mir0, H.mirror);
     // open surfaces: the boundary rows (fewer incident triangles than
     // neighbours: the diagonal block's contribution list has one entry per
     // incident triangle) and one ring of their neighbours, for k_bsweep: 2
@@ -2914,12 +2916,12 @@ int mof_test_amg_vcycle(mof_mesh *m, int32_t B, const float *r, const int32_t *s
         mof::AmgDevice &G = *Gp;
         mof::Workspace &w = m->ws;
         MOF_REQUIRE(B >= 1 && B <= G.cap && B <= w.cap, "the handle's last batch had fewer systems");
-        MOF_REQUIRE(m->n_own == m->N, "a decomposed part's handle");
         MOF_REQUIRE(!smap || (nl >= 1 && nl <= B), "bad system map");
         for (int32_t l = 0; smap && l < nl; ++l) MOF_REQUIRE(smap[l] >= 0 && smap[l] < B, "bad system map");
         for (int32_t k = 0; k < nsys; ++k)
             MOF_REQUIRE(systems && systems[k] >= 0 && systems[k] < B, "bad system to read back");
-        const bool zhb = zh < 0 ? G.regular : zh != 0;
+        // a decomposed part: the cycle as pcg_dd runs it (float2 z, the sums over the owned rows)
+        const bool zhb = zh < 0 ? (G.regular && m->n_own == m->N) : zh != 0;
         const int32_t L = (int32_t)G.lv.size();
         const size_t N = (size_t)m->N, nv = N * B;
         mof::DeviceGuard dg(m->device);
@@ -2954,7 +2956,7 @@ int mof_test_amg_vcycle(mof_mesh *m, int32_t B, const float *r, const int32_t *s
         const size_t nrec = (size_t)2 * B * w.nblk;
         MOF_REQUIRE(w.part_rzrr.n >= nrec, "partial records smaller than the batch");
         MOF_HIP(hipMemsetAsync(w.part_rzrr.p, 0, sizeof(double) * nrec, s));
-        mof::amg_vcycle(m, B, rv, zv, w.part_rzrr.p, w.nblk, mof::RedArgs{1, 0, w.nblk, m->N}, s, zhb,
+        mof::amg_vcycle(m, B, rv, zv, w.part_rzrr.p, w.nblk, mof::RedArgs{1, 0, w.nblk, m->n_own}, s, zhb,
                         smap ? dmap.p : nullptr, nl, tap ? dtap.p : nullptr);
         MOF_HIP(hipStreamSynchronize(s));
         MOF_HIP(hipMemcpy(z, zv, sizeof(uint32_t) * (zhb ? 1 : 2) * nv, hipMemcpyDeviceToHost));

@@ -14,11 +14,13 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -47,6 +49,12 @@ struct RcclApi {
     ncclResult_t (*group_end)() = nullptr;
     const char *(*error_string)(ncclResult_t) = nullptr;
 };
+
+// launches so far in this process (mof_dd_test_launches): k_halo_pull,
+// k_halo_pack, k_halo_unpack as <float> then <double>, k_dd_scatter,
+// k_dd_own_pack, k_dd_own_scatter
+constexpr int kDdKernels = 9;
+std::atomic<int64_t> g_dd_launches[kDdKernels];
 
 namespace {
 
@@ -258,6 +266,7 @@ void dd_halo(mof_dd *d, int32_t B, bool f32, int which, hipStream_t s) {
         const int64_t n = d->n_halo;
         if (n == 0) return;
         void *const *tab = d->vbase.p + (which ? d->P : 0);
+        ++g_dd_launches[f32 ? 0 : 1];
         if (f32)
             k_halo_pull<float><<<blocks(n), kWG, 0, s>>>(n, B, d->halo.p, tab, d->nloc.p);
         else
@@ -279,6 +288,7 @@ void dd_halo(mof_dd *d, int32_t B, bool f32, int which, hipStream_t s) {
         const int64_t ns = (int64_t)D.send_idx.size();
         if (ns == 0) continue;
         const int4 *ent = d->send_ent.p + d->send_base[l];
+        ++g_dd_launches[f32 ? 2 : 3];
         if (f32)
             k_halo_pack<float><<<blocks(ns), kWG, 0, s>>>(ns, B, D.n_loc(), ent, static_cast<const float *>(vec(l)),
                                                           reinterpret_cast<float *>(sptr(l, 0)));
@@ -345,6 +355,7 @@ void dd_halo(mof_dd *d, int32_t B, bool f32, int which, hipStream_t s) {
         const int64_t ng = D.n_ghost;
         if (ng == 0) continue;
         const int4 *ent = d->recv_ent.p + d->recv_base[l];
+        ++g_dd_launches[f32 ? 4 : 5];
         if (f32)
             k_halo_unpack<float><<<blocks(ng), kWG, 0, s>>>(ng, B, D.n_loc(), ent,
                                                             reinterpret_cast<const float *>(rptr(l, 0)),
@@ -362,6 +373,7 @@ void dd_gather_v(mof_dd *d, int32_t B, double *V, hipStream_t s) {
         for (size_t l = 0; l < d->parts.size(); ++l) {
             const DdPart &D = d->plan.parts[d->part_ids[l]];
             mof_mesh *m = d->parts[l];
+            ++g_dd_launches[6];
             k_dd_scatter<<<dim3(blocks(D.n_own), (unsigned)B), kWG, 0, s>>>(
                 D.n_own, D.n_loc(), d->N, d->own_l2g.p + d->own_off[l], m->ws.x64.p, m->ws.sysi.p, V);
         }
@@ -375,6 +387,7 @@ void dd_gather_v(mof_dd *d, int32_t B, double *V, hipStream_t s) {
         const int32_t p = d->part_ids[l];
         const DdPart &D = d->plan.parts[p];
         mof_mesh *m = d->parts[l];
+        ++g_dd_launches[7];
         k_dd_own_pack<<<dim3(blocks(D.n_own), (unsigned)B), kWG, 0, s>>>(D.n_own, D.n_loc(), d->nmax_own, m->ws.x64.p,
                                                                          m->ws.sysi.p, d->vgather.p + per * p);
     }
@@ -385,6 +398,7 @@ void dd_gather_v(mof_dd *d, int32_t B, double *V, hipStream_t s) {
         nccl_check(d->nccl, d->nccl->all_gather(d->vgather.p + per * d->rank, d->vgather.p, per, ncclFloat64,
                                                 static_cast<ncclComm_t>(d->comm), s),
                    "ncclAllGather(V)");
+    ++g_dd_launches[8];
     k_dd_own_scatter<<<dim3(blocks(d->nmax_own), (unsigned)B), kWG, 0, s>>>(d->P, B, d->nmax_own, d->N,
                                                                             d->all_l2g.p, d->vgather.p, V);
     MOF_HIP(hipGetLastError());
@@ -729,6 +743,135 @@ int mof_dd_get_info(const mof_dd *d, mof_dd_info *info) {
             info->max_owned = std::max(info->max_owned, D.n_own);
         }
         info->ms_setup = d->ms_setup;
+    });
+}
+
+int mof_dd_test_launches(int64_t *counts) {
+    return mof_io_guard([&] {
+        MOF_REQUIRE(counts, "NULL argument");
+        for (int k = 0; k < mof::kDdKernels; ++k) counts[k] = mof::g_dd_launches[k].load();
+    });
+}
+
+int mof_dd_test_part(mof_dd *d, int32_t l, mof_mesh **mesh, int64_t *sizes, int32_t *l2g, int32_t *ghost_owner,
+                     int32_t *ghost_src, int32_t *nbr, int32_t *recv_off, int32_t *send_off, int32_t *send_idx) {
+    return mof_io_guard([&] {
+        MOF_REQUIRE(d, "NULL argument");
+        MOF_REQUIRE(l >= 0 && (size_t)l < d->parts.size(), "no such local part");
+        const mof::DdPart &D = d->plan.parts[d->part_ids[l]];
+        if (mesh) *mesh = d->parts[l];
+        if (sizes) {
+            const int64_t v[12] = {d->part_ids[l],
+                                   D.n_own,
+                                   D.n_ghost,
+                                   (int64_t)D.nbr.size(),
+                                   (int64_t)D.send_idx.size(),
+                                   (int64_t)D.tris.size(),
+                                   d->P,
+                                   (int64_t)d->parts.size(),
+                                   d->n_halo,
+                                   d->cap,
+                                   d->nmax,
+                                   d->nmax_own};
+            std::copy(v, v + 12, sizes);
+        }
+        auto put = [](int32_t *dst, const std::vector<int32_t> &src) {
+            if (dst) std::copy(src.begin(), src.end(), dst);
+        };
+        put(l2g, D.l2g);
+        if (ghost_owner)
+            for (int32_t g = 0; g < D.n_ghost; ++g) ghost_owner[g] = d->plan.part[D.l2g[D.n_own + g]];
+        put(ghost_src, D.ghost_src);
+        put(nbr, D.nbr);
+        put(recv_off, D.recv_off);
+        put(send_off, D.send_off);
+        put(send_idx, D.send_idx);
+    });
+}
+
+namespace {
+
+// the in-process handle's workspaces hold a batch of B (a solve allocated them)
+void dd_test_ready(const mof_dd *d, int32_t B) {
+    MOF_REQUIRE(d->rank < 0, "an in-process handle only");
+    MOF_REQUIRE(B >= 1 && B <= d->cap, "the handle's workspaces hold fewer systems: solve a batch first");
+    for (const mof_mesh *m : d->parts) MOF_REQUIRE(B <= m->ws.cap, "a part's workspace holds fewer systems");
+}
+
+}  // namespace
+
+int mof_dd_test_halo(mof_dd *d, int32_t B, int32_t which, int32_t f32, const void *in, void *out,
+                     const uint32_t *sentinel) {
+    return mof_io_guard([&] {
+        using namespace mof;
+        MOF_REQUIRE(d && in && out, "NULL argument");
+        MOF_REQUIRE(which == 0 || which == 1, "which is 0 (z) or 1 (x64)");
+        MOF_REQUIRE(which == 0 || !f32, "x64 holds doubles");
+        dd_test_ready(d, B);
+        DevGuard g(d->device);
+        hipStream_t s = d->stream;
+        MOF_HIP(hipStreamSynchronize(s));
+        const size_t esz = f32 ? 4 : 8, L = d->parts.size();
+        auto vec = [&](size_t l) { return which ? (void *)d->parts[l]->ws.x64.p : (void *)d->parts[l]->ws.vz.p; };
+        auto bytes = [&](size_t l) { return esz * 2 * (size_t)B * (size_t)d->plan.parts[d->part_ids[l]].n_loc(); };
+        std::vector<std::unique_ptr<DevKeep>> keep;
+        for (size_t l = 0; l < L; ++l) keep.emplace_back(new DevKeep(vec(l), bytes(l)));
+        if (sentinel && staged(d)) {
+            MOF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d->sendbuf.p), (int)*sentinel, 2 * d->sendbuf.n, s));
+            MOF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d->recvbuf.p), (int)*sentinel, 2 * d->recvbuf.n, s));
+        }
+        size_t off = 0;
+        for (size_t l = 0; l < L; ++l) {
+            MOF_HIP(hipMemcpyAsync(vec(l), static_cast<const char *>(in) + off, bytes(l), hipMemcpyHostToDevice, s));
+            off += bytes(l);
+        }
+        dd_halo(d, B, f32 != 0, which, s);
+        MOF_HIP(hipStreamSynchronize(s));
+        off = 0;
+        for (size_t l = 0; l < L; ++l) {
+            MOF_HIP(hipMemcpy(static_cast<char *>(out) + off, vec(l), bytes(l), hipMemcpyDeviceToHost));
+            off += bytes(l);
+        }
+    });
+}
+
+int mof_dd_test_gather(mof_dd *d, int32_t B, const double *x64, const uint8_t *failed, const uint64_t *prefill,
+                       double *V) {
+    return mof_io_guard([&] {
+        using namespace mof;
+        MOF_REQUIRE(d && x64 && V, "NULL argument");
+        dd_test_ready(d, B);
+        DevGuard g(d->device);
+        hipStream_t s = d->stream;
+        MOF_HIP(hipStreamSynchronize(s));
+        const size_t L = d->parts.size(), nV = 2 * (size_t)d->N * B;
+        std::vector<std::unique_ptr<DevKeep>> keep;
+        size_t off = 0;
+        for (size_t l = 0; l < L; ++l) {
+            mof_mesh *m = d->parts[l];
+            const size_t n = 2 * (size_t)B * (size_t)d->plan.parts[d->part_ids[l]].n_loc();
+            keep.emplace_back(new DevKeep(m->ws.x64.p, n * sizeof(double)));
+            keep.emplace_back(new DevKeep(m->ws.sysi.p, sizeof(int32_t) * kSysStride * B));
+            MOF_HIP(hipMemcpyAsync(m->ws.x64.p, x64 + off, n * sizeof(double), hipMemcpyHostToDevice, s));
+            off += n;
+            if (failed) {
+                std::vector<int32_t> si((size_t)kSysStride * B);
+                MOF_HIP(hipMemcpy(si.data(), m->ws.sysi.p, si.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+                for (int32_t b = 0; b < B; ++b) si[(size_t)b * kSysStride + SI_FAILED] = failed[b] != 0;
+                MOF_HIP(hipMemcpy(m->ws.sysi.p, si.data(), si.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            }
+        }
+        DevArray<double> Vd;
+        Vd.alloc(nV);
+        if (prefill) {
+            std::vector<uint64_t> fill(std::max(nV, staged(d) ? d->vgather.n : (size_t)0), *prefill);
+            MOF_HIP(hipMemcpy(Vd.p, fill.data(), nV * sizeof(double), hipMemcpyHostToDevice));
+            if (staged(d))
+                MOF_HIP(hipMemcpy(d->vgather.p, fill.data(), d->vgather.n * sizeof(double), hipMemcpyHostToDevice));
+        }
+        dd_gather_v(d, B, Vd.p, s);
+        MOF_HIP(hipStreamSynchronize(s));
+        MOF_HIP(hipMemcpy(V, Vd.p, nV * sizeof(double), hipMemcpyDeviceToHost));
     });
 }
 

@@ -80,6 +80,18 @@ struct DevArray {
     size_t bytes() const { return n * sizeof(T); }
 };
 
+// Test hooks: a device array saved on construction and put back on destruction.
+struct DevKeep {
+    void *dev;
+    size_t bytes;
+    DevArray<char> keep;
+    DevKeep(void *p, size_t n) : dev(p), bytes(n) {
+        keep.alloc(n);
+        MOF_HIP(hipMemcpy(keep.p, dev, bytes, hipMemcpyDeviceToDevice));
+    }
+    ~DevKeep() { (void)hipMemcpy(dev, keep.p, bytes, hipMemcpyDeviceToDevice); }
+};
+
 // SELL slot of block t (vcol order) of a row whose diagonal block is its
 // td-th: the diagonal goes first, so each wave of a per-position kernel (one
 // slot of 64 rows) holds only diagonal or only off-diagonal blocks -- the

@@ -41,6 +41,7 @@
 #include <cstdlib>
 #include <chrono>
 #include <cmath>
+#include <memory>
 
 #include <hip/hip_ext.h>
 
@@ -2240,7 +2241,8 @@ int64_t pcg_dd(mof_dd *d, int32_t B, bool first_outer, double rtol, const SolveP
         chunk = 8;
     }
     if (!done) {
-        spmv(false, it);
+        // (it == 0 only with max_iter = 0, the test hook's cap 0: the first instance, as in pcg())
+        spmv(it == 0, it);
         if (sp.fail_at_max_iter)
             for (size_t l = 0; l < L; ++l)
                 k_fail_running<<<dim3((unsigned)((B + 63) / 64)), 64, 0, s>>>(B, it, args[l].sysi);
@@ -2578,6 +2580,128 @@ void test_pcg_inner(mof_mesh *m, int32_t B, const double *rhs, double rtol, doub
     }
 }
 
+// mof_dd_test_pcg_inner for one working type
+template <typename V>
+void test_pcg_dd_inner(mof_dd *d, int32_t B, const double *rhs, double rtol, bool amg, int32_t max_iter,
+                       const uint32_t *sentinel, void *x, void *r, void *z, void *p, void *q, int32_t *sysi,
+                       double *sysd, void *dinv, int32_t a_system, void *A, double *part_rzrr, double *part_pq,
+                       double *scal, int32_t *meta) {
+    constexpr bool f32 = sizeof(V) == 4;
+    const size_t L = d->parts.size();
+    MOF_REQUIRE(d->rank < 0, "an in-process handle only");
+    MOF_REQUIRE(B >= 1 && B <= d->cap && d->nmax > 0, "the handle's last batch had fewer systems");
+    MOF_REQUIRE(max_iter >= 0, "negative iteration cap");
+    MOF_REQUIRE(!amg || f32, "the multigrid preconditions the fp32 inner solve only");
+    MOF_REQUIRE(a_system < B, "bad system to read back");
+    for (mof_mesh *m : d->parts) {
+        const Workspace &w = m->ws;
+        const size_t snb = (size_t)m->pat.sell_nb();
+        MOF_REQUIRE(B <= w.cap && w.nblk > 0, "a part's last batch had fewer systems");
+        if (f32)
+            MOF_REQUIRE(w.A32.n >= 4 * snb * B, "no fp32 operator: the last solve was not mixed-precision");
+        else
+            MOF_REQUIRE(w.A64.n >= 4 * snb * B, "no fp64 operator: the last solve was not an fp64 one");
+        if (amg) {
+            MOF_REQUIRE(m->amg && amg_levels(m) >= 2, "a part has no built multigrid");
+            MOF_REQUIRE(B <= amg_capacity(m), "a part's multigrid storage holds fewer systems");
+        }
+    }
+    hipStream_t s = d->stream;
+    MOF_HIP(hipStreamSynchronize(s));
+    std::vector<std::unique_ptr<DevKeep>> keep;
+    std::vector<std::unique_ptr<SysSwap>> swap;
+    size_t off = 0;
+    for (size_t l = 0; l < L; ++l) {
+        mof_mesh *m = d->parts[l];
+        Workspace &w = m->ws;
+        const size_t nv = (size_t)m->N * B;
+        keep.emplace_back(new DevKeep(w.rhs.p, sizeof(double) * 2 * nv));
+        MOF_HIP(hipMemcpy(w.rhs.p, rhs + off, sizeof(double) * 2 * nv, hipMemcpyHostToDevice));
+        off += 2 * nv;
+        swap.emplace_back(new SysSwap(m, B, nullptr));
+        if (sentinel) {
+            for (DevArray<double> *a : {&w.vx, &w.vr, &w.vz, &w.vp, &w.vq})
+                MOF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a->p), (int)*sentinel,
+                                          2 * nv * sizeof(V) / 4, s));
+            if (amg) MOF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(amg_fine(m).x0), (int)*sentinel, nv, s));
+        }
+        MOF_HIP(hipMemsetAsync(w.sc.p, 0, sizeof(double) * 6 * B, s));
+    }
+    // as solve_batch_dd: records of workgroups past a part's own count read as zero
+    MOF_HIP(hipMemsetAsync(d->part_pq.p, 0, d->part_pq.bytes(), s));
+    MOF_HIP(hipMemsetAsync(d->part_rzrr.p, 0, d->part_rzrr.bytes(), s));
+    SolveParams sp{};
+    sp.precision = f32 ? MOF_PREC_MIXED : MOF_PREC_F64;
+    sp.block_jacobi = true;
+    sp.time_spmv = false;
+    sp.amg = amg;
+    sp.max_iter = max_iter;
+    sp.max_outer = 1;
+    sp.rtol = rtol;
+    sp.inner_rtol = rtol;
+    sp.stall = amg ? kPcgStall : 0;
+    sp.fail_at_max_iter = false;
+    int32_t max_iters = 0, hint = 0;
+    const int64_t total = pcg_dd<V>(d, B, true, rtol, sp, s, &max_iters, &hint, amg);
+    // both slots' sums as part 0 forms them (k_red_rzrr, k_red_pq over the records of all parts)
+    std::vector<PcgArgs<V>> args = dd_args<V>(d, B, amg);
+    for (int32_t slot = 0; slot < 2; ++slot) {
+        k_red_rzrr<V><<<dim3((unsigned)B), kWG, 0, s>>>(args[0], slot);
+        k_red_pq<V><<<dim3((unsigned)B), kWG, 0, s>>>(args[0], slot);
+    }
+    MOF_HIP(hipGetLastError());
+    MOF_HIP(hipStreamSynchronize(s));
+    auto get = [&](void *dst, size_t at, const void *src, size_t bytes) {
+        if (dst) MOF_HIP(hipMemcpy(static_cast<char *>(dst) + at, src, bytes, hipMemcpyDeviceToHost));
+    };
+    size_t ov = 0, os = 0, od = 0, oa = 0;
+    for (size_t l = 0; l < L; ++l) {
+        mof_mesh *m = d->parts[l];
+        Workspace &w = m->ws;
+        const size_t nv = (size_t)m->N * B, snb = (size_t)m->pat.sell_nb(), vb = sizeof(V) * 2 * nv;
+        get(x, ov, w.vx.p, vb);
+        get(r, ov, w.vr.p, vb);
+        get(z, ov, w.vz.p, vb);
+        get(p, ov, w.vp.p, vb);
+        get(q, ov, w.vq.p, vb);
+        ov += vb;
+        get(sysi, os * sizeof(int32_t), w.sysi.p, sizeof(int32_t) * kSysStride * B);
+        get(sysd, os * sizeof(double), w.sysd.p, sizeof(double) * kSysStride * B);
+        os += (size_t)kSysStride * B;
+        const V *Ap, *dv;
+        if constexpr (f32) {
+            Ap = w.A32.p;
+            dv = w.dinv32.p;
+        } else {
+            Ap = w.A64.p;
+            dv = w.dinv64.p;
+        }
+        if (!amg) get(dinv, od, dv, sizeof(V) * 4 * nv);
+        od += sizeof(V) * 4 * nv;
+        if (a_system >= 0) get(A, oa, Ap + 4 * snb * (size_t)a_system, sizeof(V) * 4 * snb);
+        oa += sizeof(V) * 4 * snb;
+    }
+    const size_t rec = (size_t)d->P * B * d->nmax;
+    get(part_rzrr, 0, d->part_rzrr.p, sizeof(double) * 4 * rec);
+    get(part_pq, 0, d->part_pq.p, sizeof(double) * 2 * rec);
+    if (scal) {
+        std::vector<double> sc((size_t)6 * B);
+        get(sc.data(), 0, d->parts[0]->ws.sc.p, sizeof(double) * 6 * B);
+        for (int32_t slot = 0; slot < 2; ++slot)
+            for (int32_t b = 0; b < B; ++b) {
+                double *o = scal + 3 * ((size_t)slot * B + b);
+                o[0] = sc[2 * ((size_t)slot * B + b)];
+                o[1] = sc[2 * ((size_t)slot * B + b) + 1];
+                o[2] = sc[(size_t)4 * B + (size_t)slot * B + b];
+            }
+    }
+    if (meta) {
+        const int32_t v[6] = {d->nmax, d->P, (int32_t)std::min<int64_t>(total, INT32_MAX), max_iters, kSysStride,
+                              (int32_t)L};
+        std::copy(v, v + 6, meta);
+    }
+}
+
 }  // namespace
 
 }  // namespace mof
@@ -2604,6 +2728,23 @@ int mof_test_pcg_inner(mof_mesh *m, int32_t B, const double *rhs, double rtol, d
         else
             mof::test_pcg_inner<double>(m, B, rhs, rtol, outer_rtol, etol, amg != 0, max_iter, active, hint, sentinel,
                                         x, r, z, p, q, x0, scal, sysi, sysd, dinv, a_system, A, meta);
+    });
+}
+
+int mof_dd_test_pcg_inner(mof_dd *d, int32_t B, const double *rhs, double rtol, int32_t amg, uint32_t precision,
+                          int32_t max_iter, const uint32_t *sentinel, void *x, void *r, void *z, void *p, void *q,
+                          int32_t *sysi, double *sysd, void *dinv, int32_t a_system, void *A, double *part_rzrr,
+                          double *part_pq, double *scal, int32_t *meta) {
+    return mof_io_guard([&] {
+        MOF_REQUIRE(d && rhs, "NULL argument");
+        MOF_REQUIRE(precision == MOF_PREC_MIXED || precision == MOF_PREC_F64, "bad precision");
+        mof::PcgDeviceGuard dg(d->device);
+        if (precision == MOF_PREC_MIXED)
+            mof::test_pcg_dd_inner<float>(d, B, rhs, rtol, amg != 0, max_iter, sentinel, x, r, z, p, q, sysi, sysd,
+                                          dinv, a_system, A, part_rzrr, part_pq, scal, meta);
+        else
+            mof::test_pcg_dd_inner<double>(d, B, rhs, rtol, amg != 0, max_iter, sentinel, x, r, z, p, q, sysi, sysd,
+                                           dinv, a_system, A, part_rzrr, part_pq, scal, meta);
     });
 }
 

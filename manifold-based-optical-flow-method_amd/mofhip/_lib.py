@@ -69,6 +69,8 @@ EXPORTS = (
     "mof_test_amg_vcycle", "mof_test_amg_vcycle_tables", "mof_test_vcycle_launches",
     "mof_test_pcg_inner", "mof_test_pcg_launches", "mof_test_outer_readback",
     "mof_modes_gram", "mof_modes_project", "mof_test_modes_chunk", "mof_test_modes_pass",
+    "mof_dd_test_part", "mof_dd_test_halo", "mof_dd_test_gather", "mof_dd_test_launches",
+    "mof_dd_test_pcg_inner",
 )
 
 
@@ -249,6 +251,11 @@ def lib():
             "mof_mesh_sync": ([P], ctypes.c_int),
             "mof_dd_test_fail_recovery_alloc": ([P, i32], ctypes.c_int),
             "mof_dd_solve_range": ([P, P, P, P, i32, i32, i32, f64, P, P, P], ctypes.c_int),
+            "mof_dd_test_part": ([P, i32] + [P] * 9, ctypes.c_int),
+            "mof_dd_test_halo": ([P, i32, i32, i32, P, P, P], ctypes.c_int),
+            "mof_dd_test_gather": ([P, i32, P, P, P, P], ctypes.c_int),
+            "mof_dd_test_launches": ([P], ctypes.c_int),
+            "mof_dd_test_pcg_inner": ([P, i32, P, f64, i32, u32, i32] + [P] * 9 + [i32] + [P] * 5, ctypes.c_int),
         }
         for name, (args, res) in sig.items():
             if os.environ.get("MOFHIP_LIB") and not hasattr(L, name):

@@ -20,6 +20,7 @@ Both return V in the reference's planar layout and caller order, like
 from __future__ import annotations
 
 import ctypes
+import threading
 
 import numpy as np
 
@@ -249,3 +250,157 @@ class DecomposedMesh:
         if rc != L.MOF_E_NOCONV:
             L.check(rc)
         return st.as_dict()
+
+
+# ---- test hooks (include/mof.h, mof_dd_test_*) ---------------------------------------
+
+DD_KERNELS = ("halo_pull_f32", "halo_pull_f64", "halo_pack_f32", "halo_pack_f64", "halo_unpack_f32",
+              "halo_unpack_f64", "dd_scatter", "dd_own_pack", "dd_own_scatter")
+
+
+def dd_launches() -> dict:
+    """Tests only (mof_dd_test_launches): launches so far in this process of
+    each halo / gather kernel instance (``DD_KERNELS``)."""
+    c = np.zeros(len(DD_KERNELS), dtype=np.int64)
+    L.check(L.lib().mof_dd_test_launches(L.ptr(c)))
+    return {k: int(v) for k, v in zip(DD_KERNELS, c)}
+
+
+class PartHandle:
+    """Tests only (mof_dd_test_part): local part ``l`` of a DecomposedMesh --
+    its plan (``part, n_own, n_ghost, n_tri, l2g, ghost_owner, ghost_src, nbr,
+    recv_off, send_off, send_idx``) and its borrowed mesh handle, with the
+    ``N / handle / lock / info`` the test hooks of :mod:`mofhip.mesh` take of a
+    DeviceMesh. Valid while the DecomposedMesh is open."""
+
+    def __init__(self, dd: "DecomposedMesh", l: int):
+        f = L.lib().mof_dd_test_part
+        h = ctypes.c_void_p()
+        sz = np.zeros(12, dtype=np.int64)
+        L.check(f(dd._h, int(l), ctypes.byref(h), L.ptr(sz), *([None] * 7)))
+        self._dd, self._handle, self._lock = dd, h, threading.Lock()
+        self.part, self.n_own, self.n_ghost, nn, ns, self.n_tri = (int(v) for v in sz[:6])
+        self.nparts, self.local_parts, self.n_halo, self.cap, self.nmax, self.nmax_own = (int(v) for v in sz[6:12])
+        self.N = self.n_own + self.n_ghost
+        i32 = lambda n: np.zeros(max(int(n), 1), dtype=np.int32)  # noqa: E731
+        a = {"l2g": i32(self.N), "ghost_owner": i32(self.n_ghost), "ghost_src": i32(self.n_ghost), "nbr": i32(nn),
+             "recv_off": i32(nn + 1), "send_off": i32(nn + 1), "send_idx": i32(ns)}
+        L.check(f(dd._h, int(l), None, None, *(L.ptr(a[k]) for k in a)))
+        n = {"l2g": self.N, "ghost_owner": self.n_ghost, "ghost_src": self.n_ghost, "nbr": nn, "recv_off": nn + 1,
+             "send_off": nn + 1, "send_idx": ns}
+        for k, v in a.items():
+            setattr(self, k, v[:n[k]].copy())
+
+    def handle(self, device=None):
+        return self._handle
+
+    def lock(self, device=None):
+        return self._lock
+
+    def info(self, device=None) -> dict:
+        inf = L.MofMeshInfo()
+        L.check(L.lib().mof_mesh_get_info(self._handle, ctypes.byref(inf)))
+        return {k: getattr(inf, k) for k, _ in inf._fields_}
+
+
+def dd_parts(dd: "DecomposedMesh") -> list:
+    """Tests only: the PartHandle of every local part."""
+    first = PartHandle(dd, 0)
+    return [first] + [PartHandle(dd, l) for l in range(1, first.local_parts)]
+
+
+def _cat(vecs, dtype):
+    return np.ascontiguousarray(np.concatenate([np.ascontiguousarray(v, dtype=dtype).ravel() for v in vecs]))
+
+
+def _split(flat, parts, B, per=2):
+    out, q = [], 0
+    for p in parts:
+        n = B * p.N * per
+        out.append(flat[q:q + n].reshape(B, p.N, per).copy())
+        q += n
+    return out
+
+
+def dd_halo(dd: "DecomposedMesh", parts, vecs, which: int, f32: bool, sentinel=None) -> list:
+    """Tests only (mof_dd_test_halo): the production halo exchange on ``vecs``
+    (one (B, n_loc, 2) array per part) put into every part's z (``which`` 0;
+    float32 with ``f32``) or x64 (``which`` 1); returns the vectors after it.
+    ``sentinel``: the word the staging buffers are filled with beforehand."""
+    dt = np.float32 if f32 else np.float64
+    B = vecs[0].shape[0]
+    assert all(v.shape == (B, p.N, 2) for v, p in zip(vecs, parts))
+    src = _cat(vecs, dt)
+    out = np.zeros_like(src)
+    sw = None if sentinel is None else np.array([sentinel], dtype=np.uint32)
+    L.check(L.lib().mof_dd_test_halo(dd._h, B, int(which), int(bool(f32)), L.ptr(src), L.ptr(out),
+                                     None if sw is None else L.ptr(sw)))
+    return _split(out, parts, B)
+
+
+def dd_gather(dd: "DecomposedMesh", parts, x64, failed=None, prefill=None) -> np.ndarray:
+    """Tests only (mof_dd_test_gather): the production gather of V (B, 2 N)
+    from ``x64`` (one (B, n_loc, 2) array per part) and the per-system
+    ``failed`` flags; ``prefill``: the 64-bit word V holds beforehand."""
+    B = x64[0].shape[0]
+    assert all(v.shape == (B, p.N, 2) for v, p in zip(x64, parts))
+    src = _cat(x64, np.float64)
+    V = np.zeros((B, 2 * dd.N))
+    fl = None if failed is None else np.ascontiguousarray(failed, dtype=np.uint8)
+    assert fl is None or fl.shape == (B,)
+    pf = None if prefill is None else np.array([prefill], dtype=np.uint64)
+    L.check(L.lib().mof_dd_test_gather(dd._h, B, L.ptr(src), None if fl is None else L.ptr(fl),
+                                       None if pf is None else L.ptr(pf), L.ptr(V)))
+    return V
+
+
+def dd_pcg_inner(dd: "DecomposedMesh", parts, rhs, rtol, cap, precond="jacobi", precision="mixed", sentinel=None,
+                 a_system=-1) -> dict:
+    """Tests only (mof_dd_test_pcg_inner): the production decomposed inner PCG
+    of the handle's last batch on ``rhs`` (one (B, n_loc, 2) float64 array per
+    part, local order), capped at ``cap`` iterations. Returns ``parts``: per
+    part a dict in the format of :func:`mofhip.mesh.pcg_inner` (``x, r, z, p,
+    q, words, z_words, sys, dinv, A`` and the shared ``scal``), plus the shared
+    ``scal`` (2 slots, B, 3), ``part_rzrr`` (2, P, B, nmax, 2), ``part_pq`` (2, P, B,
+    nmax), ``nmax, iterations, slowest``."""
+    from .mesh import SYS_STRIDE, _sys_rows
+    B = rhs[0].shape[0]
+    assert all(v.shape == (B, p.N, 2) for v, p in zip(rhs, parts))
+    amg = {"jacobi": 0, "amg": 1}[precond]
+    dt = {"mixed": np.float32, "f64": np.float64}[precision]
+    wt = {"mixed": np.uint32, "f64": np.uint64}[precision]
+    src = _cat(rhs, np.float64)
+    nloc = sum(p.N for p in parts)
+    nbs = [int(p.info()["sell_blocks"]) for p in parts]
+    vec = {k: np.zeros(B * nloc * 2, dtype=wt) for k in "xrzpq"}
+    si = np.zeros((len(parts), B, SYS_STRIDE), dtype=np.int32)
+    sd = np.zeros((len(parts), B, SYS_STRIDE), dtype=np.float64)
+    dinv = np.zeros(B * nloc * 4, dtype=dt)
+    A = np.zeros(sum(nbs) * 4, dtype=dt)
+    meta = np.zeros(6, dtype=np.int32)
+    P = parts[0].nparts
+    nmax = PartHandle(dd, 0).nmax  # as the last solve left it
+    rzrr = np.zeros((2, P, B, nmax, 2))
+    pq = np.zeros((2, P, B, nmax))
+    scal = np.zeros((2, B, 3))
+    sw = None if sentinel is None else np.array([sentinel], dtype=np.uint32)
+    L.check(L.lib().mof_dd_test_pcg_inner(
+        dd._h, B, L.ptr(src), float(rtol), amg, {"mixed": L.MOF_PREC_MIXED, "f64": L.MOF_PREC_F64}[precision], int(cap),
+        None if sw is None else L.ptr(sw), L.ptr(vec["x"]), L.ptr(vec["r"]), L.ptr(vec["z"]), L.ptr(vec["p"]),
+        L.ptr(vec["q"]), L.ptr(si), L.ptr(sd), L.ptr(dinv), int(a_system), L.ptr(A), L.ptr(rzrr), L.ptr(pq),
+        L.ptr(scal), L.ptr(meta)))
+    assert meta[0] == nmax and meta[1] == P and meta[4] == SYS_STRIDE and meta[5] == len(parts), meta
+    sp = {k: _split(vec[k], parts, B) for k in "xrzpq"}
+    dv = _split(dinv, parts, B, 4)
+    out = {"parts": [], "scal": scal, "part_rzrr": rzrr, "part_pq": pq, "nmax": nmax, "iterations": int(meta[2]),
+           "slowest": int(meta[3])}
+    q = 0
+    for l, p in enumerate(parts):
+        o = {k: sp[k][l].view(dt) for k in "xrzpq"}
+        o["words"] = {k: sp[k][l] for k in "xrzpq"}
+        o["z_words"] = sp["z"][l]
+        o.update(scal=scal, sys=_sys_rows(si[l], sd[l]), dinv=None if amg else dv[l].reshape(B, p.N, 2, 2),
+                 A=A[q:q + 4 * nbs[l]].reshape(nbs[l], 2, 2).copy() if a_system >= 0 else None)
+        q += 4 * nbs[l]
+        out["parts"].append(o)
+    return out

@@ -318,7 +318,8 @@ def from_csr(A):
     A = sp.csr_matrix(A)
     op = Op.__new__(Op)
     op.A, op.Aabs, op.n = A, abs(A), A.shape[0]
-    blk = sp.csr_matrix((np.ones(A.nnz), A.indices // 2, A.indptr), shape=(A.shape[0], A.shape[1] // 2))
+    # (a copy of indptr: sum_duplicates compacts it in place, and A keeps its own)
+    blk = sp.csr_matrix((np.ones(A.nnz), A.indices // 2, A.indptr.copy()), shape=(A.shape[0], A.shape[1] // 2))
     blk.sum_duplicates()
     op.w = np.diff(blk.indptr).astype(np.float64)
     return op
