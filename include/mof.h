@@ -922,6 +922,40 @@ int mof_test_modes_chunk(int32_t cols);
  * depend on it. */
 int mof_test_modes_pass(int32_t rows);
 
+/* ---- potentials on the mesh from the electrodes -- the
+ * evaluation half of the reference's S2_interpolate.py and
+ * S2_interpolate_phases.py ------------------------------------------------------
+ * The scripts build scipy.interpolate.Rbf(x, y, z, d) per frame with all
+ * defaults (multiquadric, euclidean norm, smooth 0). Its E x E matrix does not
+ * depend on the frame: the weights ("nodes") of all frames are one solve, the
+ * caller's (mofhip/interp.py: numpy; the library links no LAPACK), and
+ *   out[t][i] = sum_e W[t][e] phi(i, e),
+ *   r = sqrt((dx dx + dy dy) + dz dz), q = (1.0 / epsilon) r, phi = sqrt(q q + 1)
+ * for the points (N, 3) and electrodes (E, 3), W_re (T, E), out (T, N), all
+ * fp64 row-major. phi is these statements in fp64 without contraction and with
+ * correctly rounded square roots: scipy's cdist and multiquadric bit for bit.
+ * With W_im (T, E) the imaginary plane is evaluated the same way into out_im
+ * (T, N); with MOF_RBF_ANGLE (W_im required, out_im unused and may be NULL)
+ * out = atan2(im, re) of the complex interpolant, the phase script's np.angle.
+ * The sum over the electrodes runs on the fp64 matrix cores in chunks of four
+ * in ascending order in one accumulator per entry, without atomics: the same
+ * bits from run to run. The frames go through in passes of bounded size (at
+ * most 4096 frames, and from host memory at most 256 MiB of staged output), so
+ * the device workspace stays bounded whatever T is; the result does not depend
+ * on the pass size. phi is generated on the fly and never stored. No mesh
+ * handle is needed; host pointers, or device pointers on `device` with
+ * MOF_IO_DEVICE (stream: hipStream_t or NULL). Returns when done.
+ * MOF_E_ARG, with nothing written, for N, E or T < 1, E > 256 (the cap: a
+ * wave keeps the phi of 16 vertices x 256 electrodes in registers), epsilon
+ * not finite or <= 0, or a NULL required pointer. */
+#define MOF_RBF_ANGLE 4096u /* mof_rbf_eval: out = atan2(im, re) */
+int mof_rbf_eval(int32_t device, const double *points, int32_t N, const double *electrodes, int32_t E,
+                 double epsilon, const double *W_re, const double *W_im, int32_t T, uint32_t flags, void *stream,
+                 double *out, double *out_im);
+/* Tests only: frames per pass of mof_rbf_eval, 0 = the library's choice. The
+ * result does not depend on it. */
+int mof_test_rbf_pass(int32_t frames);
+
 /* Measurement helper for bench.py: launches the PCG SpMV kernel `reps` times
  * back to back on `batch` systems of the last solve's working set, timed with
  * HIP events on the handle's stream. Returns the mean launch time and the

@@ -19,3 +19,5 @@ from .winding import (winding_map, winding_map_device, winding_levels, winding_l
                       winding_rings, closest_vertices, calculate_winding_numbers, winding_lines)
 from .modes import (velocity_modes, velocity_modes_device, spatiotemporal_modes, modes_gram,  # noqa: F401
                     modes_project, process_V_k_to_complex, calculate_V_k_from_complex, calculate_percentages)
+from .interp import (interpolation, rbf_epsilon, rbf_matrix, rbf_weights, rbf_eval,  # noqa: F401
+                     rbf_eval_device)

@@ -45,6 +45,7 @@ MOF_DD_STAGED = 64
 MOF_WAVE_PHASE = 512
 MOF_WIND_ALL_LEVELS = 1024
 MOF_MODES_COMPLEX = 2048
+MOF_RBF_ANGLE = 4096
 MOF_CSR_A2 = 0
 MOF_CSR_A_LAST = 1
 
@@ -70,7 +71,7 @@ EXPORTS = (
     "mof_test_pcg_inner", "mof_test_pcg_launches", "mof_test_outer_readback",
     "mof_modes_gram", "mof_modes_project", "mof_test_modes_chunk", "mof_test_modes_pass",
     "mof_dd_test_part", "mof_dd_test_halo", "mof_dd_test_gather", "mof_dd_test_launches",
-    "mof_dd_test_pcg_inner",
+    "mof_dd_test_pcg_inner", "mof_rbf_eval", "mof_test_rbf_pass",
 )
 
 
@@ -209,6 +210,8 @@ def lib():
             "mof_modes_project": ([i32, P, i32, i32, P, P, i32, u32, P, P, P], ctypes.c_int),
             "mof_test_modes_chunk": ([i32], ctypes.c_int),
             "mof_test_modes_pass": ([i32], ctypes.c_int),
+            "mof_rbf_eval": ([i32, P, i32, P, i32, f64, P, P, i32, u32, P, P, P], ctypes.c_int),
+            "mof_test_rbf_pass": ([i32], ctypes.c_int),
             "mof_singularities": ([i32, P, P, i32, i32, P, i32, f64, u32, P, P, P, P, P],
                                   ctypes.c_int),
             "mof_amg_probe": ([P, P, i32, i32, P, P, P, P], ctypes.c_int),
