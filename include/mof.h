@@ -526,15 +526,15 @@ int mof_test_amg_levels(mof_mesh *mesh, int32_t level, int32_t *n_levels, int64_
 int mof_test_amg_readback(mof_mesh *mesh, int32_t level, int32_t system, float *A, uint32_t *Dh, uint16_t *Dh22,
                           uint32_t *Ah, uint16_t *Ah22, float *cinv);
 /* Test hook (never read from the environment): while on, every multigrid
- * setup takes the per-position Galerkin products (k_galerkin0_ns,
- * k_galerkin3_ns) that otherwise only run where a by-entry grid would pass
+ * setup takes the per-position Galerkin products (k_galerkin_ns<2>,
+ * k_galerkin_ns<3>) that otherwise only run where a by-entry grid would pass
  * 2^32 work-items -- their results are compared with the by-entry kernels' bit
  * for bit. A smoothed level 0's products by system slab stay (0: back to the
  * default). */
 int mof_test_force_galerkin_ns(int32_t on);
-/* Test hook: counts[0..8) = launches so far in this process of k_galerkin0_ns,
- * k_galerkin0_ent, k_galerkin_sys<2> from the fp32 and from the bf16 slab,
- * k_galerkin_sys<3>, k_galerkin3_ns, k_galerkin3_ent and k_galerkin3_big. */
+/* Test hook: counts[0..8) = launches so far in this process of k_galerkin_ns<2>,
+ * k_galerkin_ent<2>, k_galerkin_sys<2> from the fp32 and from the bf16 slab,
+ * k_galerkin_sys<3>, k_galerkin_ns<3>, k_galerkin_ent<3> and k_galerkin3_big. */
 int mof_test_galerkin_launches(int64_t *counts);
 /* Test hook: the production V-cycle (amg_vcycle, its own launches) applied to
  * a given residual. The handle has just solved exactly one batch of B systems

@@ -142,7 +142,7 @@ struct AmgDevLevel {
     DevArray<uint32_t> Dh;       // [B][n][4] 3x3 D^-1 bf16 entries 0..7 (level >= 1)
     DevArray<uint16_t> Dh22;     // [B][n] entry (2,2)
     DevArray<uint32_t> Ah;       // sweep copy (not the coarsest), st_a9: [B][sell_nb][2] int8 codes 0..7
-    DevArray<uint16_t> Ah22;     // [B][sell_nb][2] code 8 | bf16 scale (MOF_COARSE_I8=0: [4] / [1] bf16)
+    DevArray<uint16_t> Ah22;     // [B][sell_nb][2] code 8 | bf16 scale
     DevArray<float> slab;        // level 1 of a smoothed level 0: one system slab's A as
                                  // [sell_nb][64][12] (k_galerkin_sys<2> -> <3>)
     DevArray<float> b, x, r, y;  // [B][n][4] (level >= 1); level 0: x [B][n][2], r bf16 pairs [B][n]
@@ -155,7 +155,9 @@ struct AmgDevice {
     int32_t nc = 0;  // coarsest dofs (dense)
     float omega = 0.85f, omega1 = 1.05f;
     int32_t xm = 2;  // level 0's corrected iterate: 1 in the x0 format in place, 2 fp32 in lv[0].y
-    bool regular = false;  // tentative prolongator on a regular mesh: the bf16 iterates and omega1 1.1
+    bool regular = false;  // a regular closed mesh (no automatic smoothing of level 0, no boundary), whichever
+    // prolongator level 0 got -- a folded mesh has a smoothed one and is regular: the bf16 iterates,
+    // omega1 1.1 and, under a smoothed level 0, the bf16 slab
     // (one block-Jacobi sweep per side on the coarse levels; 2 measured in
     // round 5, profiles/r05_ab/nu1/: fewer its, fewer timesteps/s but on F3)
     // open surfaces: extra level-0 sweeps on the boundary rows and their

@@ -2,10 +2,12 @@
 //
 // Per batch of B systems (timesteps) the mesh-only hierarchy of
 // mof_amg_host.cpp gets its per-timestep values:
-//   k_galerkin0_ns /   A_{l+1} = Q^T A_l Q, one coarse block of 4 systems per
-//   k_galerkin3_ns     thread, folded over the pre-built gather lists (no
+//   k_galerkin_ns      A_{l+1} = Q^T A_l Q, one coarse block of 4 systems per
+//                      thread, folded over the pre-built gather lists (no
 //                      atomics), plus the 3x3 block-Jacobi inverse of each
-//                      coarse node;
+//                      coarse node (k_galerkin_ent, k_galerkin3_big and
+//                      k_galerkin_sys: the same sums by gather entry, by
+//                      chunk and by system slab);
 //   k_coarse_inverse   the coarsest operator (<= 128 dofs) inverted by the
 //                      symmetric sweep operator in registers (fp64, one
 //                      workgroup per system).
@@ -32,6 +34,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "mof_amg.h"
 #include "mof_rowkern.h"
@@ -218,6 +221,125 @@ __device__ __forceinline__ void st_pair(float *__restrict__ Ac, uint4 *__restric
     }
 }
 
+// What every Galerkin product A_c = P^T A_f P takes (gal_args): the coarse
+// target, the fine level's gather lists and the batch
+struct GalArgs {
+    int64_t c_sell_nb;                       // the target's SELL positions per system
+    int32_t nC;                              // and nodes
+    int32_t B;                               // systems of the batch
+    const int32_t *__restrict__ sell_row;    // the target's row of each position (>= nC: padding)
+    const int32_t *__restrict__ diag;        // each row's diagonal position
+    const uint8_t *__restrict__ dead;        // [nC][3] dofs without a prolongator column
+    const int32_t *__restrict__ twin;        // each upper block's lower twin position, or -1
+    const int32_t *__restrict__ gptr;        // [c_sell_nb + 1] each position's range of gather entries
+    const int32_t *__restrict__ gent;        // triples {fine position, P block of i, P block of j}
+    const float *__restrict__ Q;             // P blocks
+    float *__restrict__ Ac;                  // [B][c_sell_nb][12]
+    uint4 *__restrict__ Dh;                  // [B][nC] block-Jacobi D^-1 (st_h9)
+    uint16_t *__restrict__ Dh22;
+    uint4 *__restrict__ Ah;                  // [B][c_sell_nb] sweep copy (st_a9), or null (the coarsest)
+    uint16_t *__restrict__ Ah22;
+};
+
+// where a product reads its fine blocks: level 0's bf16 sweep copy (uint2) or
+// fp32 A (float4) per block, a level >= 1's fp32 A (12 floats per block)
+template <int BSF, bool H>
+using GalSrc = std::conditional_t<BSF == 3, float, std::conditional_t<H, uint2, float4>>;
+
+// a P block: BSF x 3 floats, row-major (q[k * 3 + c])
+template <int BSF>
+__device__ __forceinline__ void ld_p(const float *__restrict__ Q, int32_t blk, float (&q)[3 * BSF]) {
+#pragma unroll
+    for (int k = 0; k < 3 * BSF; ++k) q[k] = Q[(int64_t)blk * (3 * BSF) + k];
+}
+
+// The fine block of gather entry fp, at A[base + position * stride] (a
+// system's operator: base = b * sell_nb, stride 1; a system slab: base =
+// lane, stride kSlab). A level-0 entry with kMirT is the upper twin, read
+// transposed. fp < 0 is a decomposed part's ghost block: the identity for
+// -1, zero otherwise. Position 0 is read for it and dropped: a branch around
+// the loads costs k_galerkin3_big and k_galerkin_ns<3> registers across an
+// occupancy step (81 and 138 VGPRs; profiles/galerkin_refactor/).
+template <int BSF, typename T>
+__device__ __forceinline__ void ld_fine(const T *__restrict__ A, int64_t base, int64_t stride, int32_t fp,
+                                        float (&a)[BSF][BSF]) {
+    if constexpr (BSF == 3) {
+        ldm<3>(A, base + max(fp, 0) * stride, a);
+    } else {
+        const int64_t q = base + (fp < 0 ? 0 : fp & kMirPos) * stride;
+        if constexpr (std::is_same_v<T, uint2>) {
+            h0_dec(h0_ld(A, q), a[0][0], a[0][1], a[1][0], a[1][1]);
+        } else {
+            const float4 v = A[q];
+            a[0][0] = v.x; a[0][1] = v.y; a[1][0] = v.z; a[1][1] = v.w;
+        }
+        if (fp >= 0 && (fp & kMirT)) {
+            const float t01 = a[0][1];
+            a[0][1] = a[1][0];
+            a[1][0] = t01;
+        }
+    }
+    if (fp < 0) {
+#pragma unroll
+        for (int r = 0; r < BSF; ++r)
+#pragma unroll
+            for (int c = 0; c < BSF; ++c) a[r][c] = (fp == -1 && r == c) ? 1.f : 0.f;
+    }
+}
+
+// One term out = Q_i^T (A Q_j) of a product. No fp contraction, and the
+// pragma is lexical -- it has to stand here, a caller's does not reach an
+// inlined body: the kernels with several systems per thread unroll over them,
+// and every system slot must round alike (a system's bits must not depend on
+// its slot, i.e. on the batch split). k_galerkin_sys alone keeps a contracted
+// form of its own.
+template <int BSF>
+__device__ __forceinline__ void gal_term(const float (&a)[BSF][BSF], const float (&qi)[3 * BSF],
+                                         const float (&qj)[3 * BSF], float (&out)[3][3]) {
+#pragma clang fp contract(off)
+    float T[BSF][3];  // A Q_j
+#pragma unroll
+    for (int r = 0; r < BSF; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float sum = 0.f;
+#pragma unroll
+            for (int k = 0; k < BSF; ++k) sum += a[r][k] * qj[k * 3 + c];
+            T[r][c] = sum;
+        }
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float sum = 0.f;
+#pragma unroll
+            for (int k = 0; k < BSF; ++k) sum += qi[k * 3 + r] * T[k][c];
+            out[r][c] = sum;
+        }
+}
+
+// The folded block Cm of position pos (row I) of system b goes to the target:
+// a diagonal block (diag) gets 1 on its dead dofs, is made symmetric to the
+// bit (sym3) and leaves its inverse as the level's D^-1; then the block and
+// its lower twin (st_pair), whose position is returned (-1: none)
+__device__ __forceinline__ int32_t gal_finish(const GalArgs &g, int32_t b, int64_t pos, int32_t I, bool diag,
+                                              float (&Cm)[3][3]) {
+    // read ahead of the stores: __restrict__ on a member promises the
+    // compiler nothing, so it would not move this load above them itself
+    const int32_t tw = g.twin[pos];
+    if (diag) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d)
+            if (g.dead[3 * (int64_t)I + d]) Cm[d][d] += 1.f;
+        sym3(Cm);
+        float D[3][3];
+        inv3(Cm, D);
+        st_h9(g.Dh, g.Dh22, (int64_t)b * g.nC + I, D);
+    }
+    st_pair(g.Ac, g.Ah, g.Ah22, b, g.c_sell_nb, pos, tw, Cm);
+    return tw;
+}
+
 // ---- per-timestep setup --------------------------------------------------
 
 // A32 -> the level-0 sweep copy (h0_st)
@@ -246,219 +368,140 @@ __global__ __launch_bounds__(kWG) void k_h0_twins(int64_t nb, const int32_t *__r
     H[o + p] = h0_tr(h0_ld(H, o + (mr & kMirPos)));
 }
 
-// Level 0's Galerkin product with kNS systems per thread: the gather entry
-// (fine position, P blocks of i and j) and both P blocks are loaded once and
-// applied to the fine blocks of every system (level 0 has 7.5x the entries
-// with a smoothed prolongator). Fine blocks from the smoother's bf16 copy
-// (Afh) or the fp32 A (Af), folded per system in list order.
-// Systems per thread: C3 (512 systems) 6.08 ms per launch at 4, 8.06 at 8,
-// 14.7 at 16 (the per-system fine-block gathers, not the shared gather
+// The Galerkin product per coarse position, NS systems per thread: the
+// gather entry (fine position, P blocks of i and j) and both P blocks are
+// loaded once and applied to the fine blocks of every system, folded per
+// system in list order. Level 0 (BSF = 2; 7.5x the entries with a smoothed
+// prolongator) reads the smoother's bf16 copy (Afh) or, Afh null, the fp32 A
+// (Af); levels >= 1 (BSF = 3) the fp32 3x3 blocks of Af.
+// Level 0, systems per thread: C3 (512 systems) 6.08 ms per launch at 4, 8.06
+// at 8, 14.7 at 16 (the per-system fine-block gathers, not the shared gather
 // lists, bound it; more systems per thread only lower the occupancy); one
-// system per thread (k_galerkin<2>): 9.02 ms.
+// system per thread (k_galerkin<2>): 9.02 ms. One gather entry per load
+// batch (92 VGPRs, 5 waves per SIMD) instead of 2 (140, 3 waves): 6.37 ->
+// 5.92 ms per launch (round 3).
 // The system quads of a coarse tile run back to back on an XCD in groups of
 // kGrpGal (8 quads = 32 systems); 2 quads per group (fewer systems' fine
 // blocks in flight per tile) measured slower: C3 3424-3428 vs 3443-3446
 // timesteps/s (round 3, profiles/r03_ab/gal2_*).
+// Level 1 at C3 (512 systems): 1217 us per launch with one system per thread
+// (round 2's k_galerkin<3>, 4 entries per load batch), 935 with 2, 851 with 4
+// (132 VGPRs, 3 waves); C3 +0.5 %, R3 (denser level 1) within noise (round 3).
 constexpr int kGalNS = 4;
-__global__ __launch_bounds__(kWG) void k_galerkin0_ns(
-    int64_t c_sell_nb, int32_t nC, int32_t B, const int32_t *__restrict__ c_sell_row,
-    const int32_t *__restrict__ c_diag, const uint8_t *__restrict__ c_dead, const int32_t *__restrict__ c_twin,
-    const int32_t *__restrict__ gptr, const int32_t *__restrict__ gent, const float *__restrict__ Q,
-    const float *__restrict__ Af, int64_t f_sell_nb, float *__restrict__ Ac, uint4 *__restrict__ Dh,
-    uint16_t *__restrict__ Dh22, uint4 *__restrict__ Ah, uint16_t *__restrict__ Ah22,
-    const uint2 *__restrict__ Afh) {
+constexpr int kGal3NS = 4;
+template <int BSF, int NS>
+__global__ __launch_bounds__(kWG) void k_galerkin_ns(GalArgs g, const float *__restrict__ Af, int64_t f_sell_nb,
+                                                     const uint2 *__restrict__ Afh) {
     // no fp contraction: every system slot of the unrolled loops rounds alike
-    // (a system's bits must not depend on its slot, i.e. on the batch split)
+    // (gal_term)
 #pragma clang fp contract(off)
     int32_t tile, bq;
-    const int32_t nq = (B + kGalNS - 1) / kGalNS;
-    if (!xcd_map((int32_t)((c_sell_nb + kWG - 1) / kWG), nq, tile, bq, kGrpGal)) return;
+    if (!xcd_map((int32_t)((g.c_sell_nb + kWG - 1) / kWG), (g.B + NS - 1) / NS, tile, bq, kGrpGal)) return;
     const int64_t pos = (int64_t)tile * kWG + threadIdx.x;
-    if (pos >= c_sell_nb) return;
-    const int32_t I = c_sell_row[pos];
-    if (I >= nC) return;
-    const int32_t b0 = bq * kGalNS;
-    float Cm[kGalNS][3][3] = {};
-    const int32_t g0 = gptr[pos], g1 = gptr[pos + 1];
-    if (g0 == g1 && pos != c_diag[I]) return;  // a lower block (its upper twin writes it, st_pair) or padding
-    // one gather entry per load batch (92 VGPRs, 5 waves per SIMD) instead
-    // of 2 (140, 3 waves): 6.37 -> 5.92 ms per launch (round 3)
-    constexpr int U = 1;
-    for (int32_t t0 = g0; t0 < g1; t0 += U) {
-        int32_t fp[U], ii[U], jj[U];
+    if (pos >= g.c_sell_nb) return;
+    const int32_t I = g.sell_row[pos];
+    if (I >= g.nC) return;
+    const int32_t b0 = bq * NS;
+    float Cm[NS][3][3] = {};
+    const int32_t e0 = g.gptr[pos], e1 = g.gptr[pos + 1];
+    const bool diag = pos == g.diag[I];
+    if (e0 == e1 && !diag) return;  // a lower block (its upper twin writes it, st_pair) or padding
+    for (int64_t e = e0; e < e1; ++e) {
+        const int32_t fp = g.gent[3 * e], ii = g.gent[3 * e + 1], jj = g.gent[3 * e + 2];
+        float qi[3 * BSF], qj[3 * BSF], a[NS][BSF][BSF];
+        ld_p<BSF>(g.Q, ii, qi);
+        ld_p<BSF>(g.Q, jj, qj);
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t g = min(t0 + u, g1 - 1);
-            fp[u] = gent[3 * g];
-            ii[u] = gent[3 * g + 1];
-            jj[u] = gent[3 * g + 2];
-        }
-        float qi[U][6], qj[U][6], a[U][kGalNS][4];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                qi[u][k] = Q[(int64_t)ii[u] * 6 + k];
-                qj[u][k] = Q[(int64_t)jj[u] * 6 + k];
-            }
-            const int32_t fq = fp[u] < 0 ? 0 : fp[u] & kMirPos;
-            const bool tr = fp[u] >= 0 && (fp[u] & kMirT);  // transposed upper block
-#pragma unroll
-            for (int t = 0; t < kGalNS; ++t) {
-                const int64_t bb = min(b0 + t, B - 1);
-                if (Afh) {
-                    h0_dec(h0_ld(Afh, bb * f_sell_nb + fq), a[u][t][0], a[u][t][1], a[u][t][2], a[u][t][3]);
-                } else {
-                    const float4 v = reinterpret_cast<const float4 *>(Af)[bb * f_sell_nb + fq];
-                    a[u][t][0] = v.x; a[u][t][1] = v.y; a[u][t][2] = v.z; a[u][t][3] = v.w;
-                }
-                if (tr) {
-                    const float t01 = a[u][t][1];
-                    a[u][t][1] = a[u][t][2];
-                    a[u][t][2] = t01;
-                }
-                if (fp[u] < 0) {  // a decomposed part's ghost block: identity / zero
-                    const float d = fp[u] == -1 ? 1.f : 0.f;
-                    a[u][t][0] = d; a[u][t][1] = 0.f; a[u][t][2] = 0.f; a[u][t][3] = d;
-                }
-            }
+        for (int t = 0; t < NS; ++t) {
+            const int64_t base = (int64_t)min(b0 + t, g.B - 1) * f_sell_nb;
+            if constexpr (BSF == 3)
+                ld_fine<3>(Af, base, 1, fp, a[t]);
+            else if (Afh)
+                ld_fine<2>(Afh, base, 1, fp, a[t]);
+            else
+                ld_fine<2>(reinterpret_cast<const float4 *>(Af), base, 1, fp, a[t]);
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const float on = t0 + u < g1 ? 1.f : 0.f;
+        for (int t = 0; t < NS; ++t) {
+            float T[3][3];
+            gal_term<BSF>(a[t], qi, qj, T);
 #pragma unroll
-            for (int t = 0; t < kGalNS; ++t) {
-                float T[2][3];  // A Q_j
-#pragma unroll
-                for (int r = 0; r < 2; ++r)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c)
-                        T[r][c] = on * (a[u][t][2 * r] * qj[u][c] + a[u][t][2 * r + 1] * qj[u][3 + c]);
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) Cm[t][r][c] += qi[u][r] * T[0][c] + qi[u][3 + r] * T[1][c];
-            }
+            for (int k = 0; k < 9; ++k) Cm[t][k / 3][k % 3] += T[k / 3][k % 3];
         }
     }
 #pragma unroll
-    for (int t = 0; t < kGalNS; ++t) {
-        const int32_t b = b0 + t;
-        if (b >= B) continue;
-        if (pos == c_diag[I]) {
-#pragma unroll
-            for (int d = 0; d < 3; ++d)
-                if (c_dead[3 * (int64_t)I + d]) Cm[t][d][d] += 1.f;
-            sym3(Cm[t]);
-            float D[3][3];
-            inv3(Cm[t], D);
-            st_h9(Dh, Dh22, (int64_t)b * nC + I, D);
-        }
-        st_pair(Ac, Ah, Ah22, b, c_sell_nb, pos, c_twin[pos], Cm[t]);
-    }
+    for (int t = 0; t < NS; ++t)
+        if (b0 + t < g.B) gal_finish(g, b0 + t, pos, I, diag, Cm[t]);
 }
 
-// Level 0's Galerkin product by gather entry (tentative prolongator): a
-// workgroup takes a range of coarse positions with at most kWG gather
-// entries in total (ggrp, built on the host), one entry per thread for
-// kGalNS systems -- the entry and its two Q rows loaded once, every fine block
-// of the systems gathered at once -- stages each term Q_i^T A_ij Q_j in LDS,
-// then one thread per (coarse position, system) sums its terms in list order.
-// The same terms in the same order as k_galerkin0_ns (bit-identical), with
-// two dependent loads per thread instead of two per entry of a position.
-// Systems per workgroup (C3, 512 systems, one box, round 3: 4 -> 5288 us per
-// launch, 4 with the first task's position data loaded beside the entry
-// 4978, 2 4670-4735, 1 5613, 8 6271; the old per-position kernel 5952, its
-// reads 32.5 -> 4.35 GB per launch). Spreading the sums over the 9 block
+// The Galerkin product by gather entry (tentative prolongator; BSF = 2:
+// level 0 from the bf16 sweep copy, BSF = 3: levels >= 1): a workgroup takes
+// a range of coarse positions with at most kWG gather entries in total
+// (ggrp, built on the host), one entry per thread for kGalENS systems -- the
+// entry and its two Q rows loaded once, every fine block of the systems
+// gathered at once -- stages each term Q_i^T A_ij Q_j in LDS, then one thread
+// per (coarse position, system) sums its terms in list order. The same terms
+// in the same order as k_galerkin_ns (bit-identical), with two dependent
+// loads per thread instead of two per entry of a position.
+// Systems per workgroup (level 0 at C3, 512 systems, one box, round 3: 4 ->
+// 5288 us per launch, 4 with the first task's position data loaded beside the
+// entry 4978, 2 4670-4735, 1 5613, 8 6271; the old per-position kernel 5952,
+// its reads 32.5 -> 4.35 GB per launch). Spreading the sums over the 9 block
 // entries (every thread busy, a second barrier) took 9376 us.
 constexpr int kGalENS = 2;
-__global__ __launch_bounds__(kWG) void k_galerkin0_ent(
-    int32_t ngrp, const int32_t *__restrict__ ggrp, int32_t nC, int32_t B, const int32_t *__restrict__ c_sell_row,
-    const int32_t *__restrict__ c_diag, const uint8_t *__restrict__ c_dead, const int32_t *__restrict__ c_twin, const int32_t *__restrict__ gptr,
-    const int32_t *__restrict__ gent, const float *__restrict__ Q, const uint2 *__restrict__ Afh,
-    int64_t f_sell_nb, int64_t c_sell_nb, float *__restrict__ Ac, uint4 *__restrict__ Dh,
-    uint16_t *__restrict__ Dh22, uint4 *__restrict__ Ah, uint16_t *__restrict__ Ah22) {
-    // no fp contraction: every system slot rounds alike, and as k_galerkin0_ns
+template <int BSF>
+__global__ __launch_bounds__(kWG) void k_galerkin_ent(GalArgs g, int32_t ngrp, const int32_t *__restrict__ ggrp,
+                                                      const GalSrc<BSF, true> *__restrict__ Af, int64_t f_sell_nb) {
+    // no fp contraction: every system slot rounds alike, and as k_galerkin_ns
 #pragma clang fp contract(off)
     __shared__ float con[kGalENS][9][kWG];
-    int32_t g, bq;
-    const int32_t nq = (B + kGalENS - 1) / kGalENS;
-    if (!xcd_map(ngrp, nq, g, bq, kGrpGal)) return;
+    int32_t grp, bq;
+    const int32_t nq = (g.B + kGalENS - 1) / kGalENS;
+    if (!xcd_map(ngrp, nq, grp, bq, kGrpGal)) return;
     const int32_t b0 = bq * kGalENS;
-    const int32_t p0 = ggrp[2 * g], p1 = ggrp[2 * g + 1];
-    const int32_t e0 = gptr[p0], e1 = gptr[p1];
-    const int32_t e = e0 + (int32_t)threadIdx.x;
+    const int32_t p0 = ggrp[2 * grp], p1 = ggrp[2 * grp + 1];
+    const int32_t e0 = g.gptr[p0], e1 = g.gptr[p1];
+    const int64_t e = e0 + (int32_t)threadIdx.x;
     const int32_t np = p1 - p0;
     // the first task's position data, loaded beside the entry's (the tasks
     // run after the barrier; most groups have one task per thread or fewer)
-    int32_t tI = nC, tq0 = 0, tq1 = 0, tdg = -1;
+    int32_t tI = g.nC, tq0 = 0, tq1 = 0, tdg = -1;
     if ((int32_t)threadIdx.x < np * kGalENS) {
         const int32_t pos = p0 + (int32_t)threadIdx.x / kGalENS;
-        tI = c_sell_row[pos];
-        tq0 = gptr[pos];
-        tq1 = gptr[pos + 1];
-        if (tI < nC) tdg = c_diag[tI];
+        tI = g.sell_row[pos];
+        tq0 = g.gptr[pos];
+        tq1 = g.gptr[pos + 1];
+        if (tI < g.nC) tdg = g.diag[tI];
     }
     if (e < e1) {
-        const int32_t fp = gent[3 * (int64_t)e], ii = gent[3 * (int64_t)e + 1], jj = gent[3 * (int64_t)e + 2];
-        float qi[6], qj[6], a[kGalENS][4];
+        const int32_t fp = g.gent[3 * e], ii = g.gent[3 * e + 1], jj = g.gent[3 * e + 2];
+        float qi[3 * BSF], qj[3 * BSF], a[kGalENS][BSF][BSF];
+        ld_p<BSF>(g.Q, ii, qi);
+        ld_p<BSF>(g.Q, jj, qj);
 #pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            qi[k] = Q[(int64_t)ii * 6 + k];
-            qj[k] = Q[(int64_t)jj * 6 + k];
-        }
-        const int32_t fq = fp < 0 ? 0 : fp & kMirPos;
-        const bool tr = fp >= 0 && (fp & kMirT);  // transposed upper block
+        for (int t = 0; t < kGalENS; ++t) ld_fine<BSF>(Af, (int64_t)min(b0 + t, g.B - 1) * f_sell_nb, 1, fp, a[t]);
 #pragma unroll
         for (int t = 0; t < kGalENS; ++t) {
-            const int64_t bb = min(b0 + t, B - 1);
-            h0_dec(h0_ld(Afh, bb * f_sell_nb + fq), a[t][0], a[t][1], a[t][2], a[t][3]);
-            if (tr) {
-                const float t01 = a[t][1];
-                a[t][1] = a[t][2];
-                a[t][2] = t01;
-            }
-            if (fp < 0) {  // a decomposed part's ghost block: identity / zero
-                const float d = fp == -1 ? 1.f : 0.f;
-                a[t][0] = d; a[t][1] = 0.f; a[t][2] = 0.f; a[t][3] = d;
-            }
-        }
+            float T[3][3];
+            gal_term<BSF>(a[t], qi, qj, T);
 #pragma unroll
-        for (int t = 0; t < kGalENS; ++t) {
-            float T[2][3];  // A Q_j
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) T[r][c] = 1.f * (a[t][2 * r] * qj[c] + a[t][2 * r + 1] * qj[3 + c]);
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) con[t][3 * r + c][threadIdx.x] = qi[r] * T[0][c] + qi[3 + r] * T[1][c];
+            for (int k = 0; k < 9; ++k) con[t][k][threadIdx.x] = T[k / 3][k % 3];
         }
     }
     __syncthreads();
     for (int32_t task = threadIdx.x; task < np * kGalENS; task += kWG) {
         const int32_t pos = p0 + task / kGalENS, t = task % kGalENS, b = b0 + t;
         const bool first = task == (int32_t)threadIdx.x;
-        const int32_t I = first ? tI : c_sell_row[pos];
-        if (I >= nC || b >= B) continue;
+        const int32_t I = first ? tI : g.sell_row[pos];
+        if (I >= g.nC || b >= g.B) continue;
         float Cm[3][3] = {};
-        const int32_t q0 = first ? tq0 : gptr[pos], q1 = first ? tq1 : gptr[pos + 1];
-        const bool diag = pos == (first ? tdg : c_diag[I]);
+        const int32_t q0 = first ? tq0 : g.gptr[pos], q1 = first ? tq1 : g.gptr[pos + 1];
+        const bool diag = pos == (first ? tdg : g.diag[I]);
         if (q0 == q1 && !diag) continue;  // a lower block (its upper twin writes it, st_pair) or padding
         for (int32_t q = q0; q < q1; ++q)
 #pragma unroll
             for (int k = 0; k < 9; ++k) Cm[k / 3][k % 3] += con[t][k][q - e0];
-        if (diag) {
-#pragma unroll
-            for (int d = 0; d < 3; ++d)
-                if (c_dead[3 * (int64_t)I + d]) Cm[d][d] += 1.f;
-            sym3(Cm);
-            float D[3][3];
-            inv3(Cm, D);
-            st_h9(Dh, Dh22, (int64_t)b * nC + I, D);
-        }
-        st_pair(Ac, Ah, Ah22, b, c_sell_nb, pos, c_twin[pos], Cm);
+        gal_finish(g, b, pos, I, diag, Cm);
     }
 }
 
@@ -506,76 +549,49 @@ __global__ __launch_bounds__(kWG) void k_a_slab(int64_t f_sell_nb, int32_t b0, i
 }
 
 constexpr int kGalSysPos = kWG / 64;  // coarse positions per workgroup, one per wave
-// Level l's Galerkin product over one system slab: BSF = 2 reads the level-0
-// slab (k_a_slab, float4 blocks or, H, bf16 as uint2; mirror entries), BSF = 3 the slab a level
-// l >= 1 product wrote beside its level's A (CS: [sell_nb][kSlab][3] float4,
-// the stored rows). Gather entries per load batch: 4 at level 0, 2 on the
-// coarse levels (their P blocks are 18 scalar registers each).
+// Level l's Galerkin product over the system slab of b0: BSF = 2 reads the
+// level-0 slab (k_a_slab, float4 blocks or, H, bf16 as uint2; mirror
+// entries), BSF = 3 the slab a level l >= 1 product wrote beside its level's
+// A (CS: [sell_nb][kSlab][3] float4, the stored rows). Gather entries per
+// load batch: 4 at level 0, 2 on the coarse levels (their P blocks are 18
+// scalar registers each).
 template <int BSF, bool H = false>
-__global__ __launch_bounds__(kWG) void k_galerkin_sys(
-    int64_t c_sell_nb, int32_t nC, int32_t B, int32_t b0, const int32_t *__restrict__ c_sell_row,
-    const int32_t *__restrict__ c_diag, const uint8_t *__restrict__ c_dead, const int32_t *__restrict__ c_twin, const int32_t *__restrict__ gptr,
-    const int32_t *__restrict__ gent, const float *__restrict__ Q, const float4 *__restrict__ FS,
-    float *__restrict__ Ac, uint4 *__restrict__ Dh, uint16_t *__restrict__ Dh22, uint4 *__restrict__ Ah,
-    uint16_t *__restrict__ Ah22, float4 *__restrict__ CS) {
+__global__ __launch_bounds__(kWG) void k_galerkin_sys(GalArgs g, const GalSrc<BSF, H> *__restrict__ FS, int32_t b0,
+                                                      float4 *__restrict__ CS) {
     constexpr int U = BSF == 2 ? 4 : 2;
-    constexpr int QS = 3 * BSF;  // floats per P block
     int32_t tile, bq;
-    if (!xcd_map((int32_t)((c_sell_nb + kGalSysPos - 1) / kGalSysPos), 1, tile, bq, 1)) return;
+    if (!xcd_map((int32_t)((g.c_sell_nb + kGalSysPos - 1) / kGalSysPos), 1, tile, bq, 1)) return;
     const int64_t pos = (int64_t)tile * kGalSysPos + __builtin_amdgcn_readfirstlane((int32_t)threadIdx.x >> 6);
-    if (pos >= c_sell_nb) return;
-    const int32_t I = c_sell_row[pos];
-    if (I >= nC) return;
+    if (pos >= g.c_sell_nb) return;
+    const int32_t I = g.sell_row[pos];
+    if (I >= g.nC) return;
     const int32_t lane = (int32_t)threadIdx.x & 63;
     float Cm[3][3] = {};
-    const int32_t g0 = gptr[pos], g1 = gptr[pos + 1];
-    if (g0 == g1 && pos != c_diag[I]) return;  // a lower block (its upper twin writes it, st_pair) or padding
+    const int32_t e0 = g.gptr[pos], e1 = g.gptr[pos + 1];
+    const bool diag = pos == g.diag[I];
+    if (e0 == e1 && !diag) return;  // a lower block (its upper twin writes it, st_pair) or padding
     // U entries per load batch (the entries' scalar loads, then their fine
-    // blocks, in flight together); a batch's tail entries past g1 are
+    // blocks, in flight together); a batch's tail entries past e1 are
     // clamped to the last one and skipped (wave-uniform)
-    for (int32_t t0 = g0; t0 < g1; t0 += U) {
+    for (int32_t t0 = e0; t0 < e1; t0 += U) {
         int32_t fp[U];
-        float qi[U][QS], qj[U][QS], a[U][BSF][BSF];
+        float qi[U][3 * BSF], qj[U][3 * BSF], a[U][BSF][BSF];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int64_t g = min(t0 + u, g1 - 1);
-            fp[u] = gent[3 * g];
-            const int32_t ii = gent[3 * g + 1], jj = gent[3 * g + 2];
-#pragma unroll
-            for (int k = 0; k < QS; ++k) {
-                qi[u][k] = Q[(int64_t)ii * QS + k];
-                qj[u][k] = Q[(int64_t)jj * QS + k];
-            }
+            const int64_t e = min(t0 + u, e1 - 1);
+            fp[u] = g.gent[3 * e];
+            ld_p<BSF>(g.Q, g.gent[3 * e + 1], qi[u]);
+            ld_p<BSF>(g.Q, g.gent[3 * e + 2], qj[u]);
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            if (fp[u] < 0) {  // a decomposed part's ghost block: identity / zero
-#pragma unroll
-                for (int r = 0; r < BSF; ++r)
-#pragma unroll
-                    for (int c = 0; c < BSF; ++c) a[u][r][c] = (fp[u] == -1 && r == c) ? 1.f : 0.f;
-            } else if constexpr (BSF == 2) {
-                const bool tr = fp[u] & kMirT;  // transposed upper block
-                if constexpr (H) {
-                    const uint2 h = reinterpret_cast<const uint2 *>(FS)[(int64_t)(fp[u] & kMirPos) * kSlab + lane];
-                    h0_dec(tr ? h0_tr(h) : h, a[u][0][0], a[u][0][1], a[u][1][0], a[u][1][1]);
-                } else {
-                    const float4 v = FS[(int64_t)(fp[u] & kMirPos) * kSlab + lane];
-                    a[u][0][0] = v.x; a[u][0][1] = tr ? v.z : v.y; a[u][1][0] = tr ? v.y : v.z; a[u][1][1] = v.w;
-                }
-            } else {
-                const float4 *p = FS + ((int64_t)fp[u] * kSlab + lane) * 3;
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    const float4 v = p[r];
-                    a[u][r][0] = v.x; a[u][r][1] = v.y; a[u][r][2] = v.z;
-                }
-            }
-        }
+        for (int u = 0; u < U; ++u) ld_fine<BSF>(FS, lane, kSlab, fp[u], a[u]);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            if (t0 + u >= g1) break;
-            // P blocks are BSF x 3, row-major: q[k * 3 + c]
+            if (t0 + u >= e1) break;
+            // gal_term's sums written out where fp contraction is on, as this
+            // kernel has always had it: each lane is one system and runs the
+            // same instructions, so contraction is uniform over the batch,
+            // and the contracted bits are the results on every smoothed mesh
             float T[BSF][3];  // A Q_j
 #pragma unroll
             for (int r = 0; r < BSF; ++r)
@@ -598,210 +614,17 @@ __global__ __launch_bounds__(kWG) void k_galerkin_sys(
         }
     }
     const int32_t b = b0 + lane;
-    if (b >= B) return;
-    if (pos == c_diag[I]) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d)
-            if (c_dead[3 * (int64_t)I + d]) Cm[d][d] += 1.f;
-        sym3(Cm);
-        float D[3][3];
-        inv3(Cm, D);
-        st_h9(Dh, Dh22, (int64_t)b * nC + I, D);
-    }
-    st_pair(Ac, Ah, Ah22, b, c_sell_nb, pos, c_twin[pos], Cm);
-    if (CS) {
+    if (b >= g.B) return;
+    const int32_t tw = gal_finish(g, b, pos, I, diag, Cm);
+    if (CS) {  // the next product's slab: the block as stored, and its lower twin
         float4 *p = CS + (pos * kSlab + lane) * 3;
 #pragma unroll
         for (int r = 0; r < 3; ++r) p[r] = make_float4(Cm[r][0], Cm[r][1], Cm[r][2], 0.f);
-        if (c_twin[pos] >= 0) {
-            float4 *q = CS + ((int64_t)c_twin[pos] * kSlab + lane) * 3;
+        if (tw >= 0) {
+            float4 *q = CS + ((int64_t)tw * kSlab + lane) * 3;
 #pragma unroll
             for (int r = 0; r < 3; ++r) q[r] = make_float4(Cm[0][r], Cm[1][r], Cm[2][r], 0.f);
         }
-    }
-}
-
-// Levels >= 1: the Galerkin product with NS systems per thread sharing each
-// gather entry and its two Q blocks (k_galerkin0_ns's scheme for the fp32
-// 3x3 blocks), folded per system in list order. Level 1 at C3 (512 systems):
-// 1217 us per launch with one system per thread (round 2's k_galerkin<3>,
-// 4 entries per load batch), 935 with 2, 851 with 4 (132 VGPRs, 3 waves);
-// C3 +0.5 %, R3 (denser level 1) within noise (round 3).
-constexpr int kGal3NS = 4;
-template <int NS>
-__global__ __launch_bounds__(kWG) void k_galerkin3_ns(
-    int64_t c_sell_nb, int32_t nC, int32_t B, const int32_t *__restrict__ c_sell_row,
-    const int32_t *__restrict__ c_diag, const uint8_t *__restrict__ c_dead, const int32_t *__restrict__ c_twin,
-    const int32_t *__restrict__ gptr, const int32_t *__restrict__ gent, const float *__restrict__ Q,
-    const float *__restrict__ Af, int64_t f_sell_nb, float *__restrict__ Ac, uint4 *__restrict__ Dh,
-    uint16_t *__restrict__ Dh22, uint4 *__restrict__ Ah, uint16_t *__restrict__ Ah22) {
-#pragma clang fp contract(off)
-    int32_t tile, bq;
-    if (!xcd_map((int32_t)((c_sell_nb + kWG - 1) / kWG), (B + NS - 1) / NS, tile, bq, kGrpGal)) return;
-    const int64_t pos = (int64_t)tile * kWG + threadIdx.x;
-    if (pos >= c_sell_nb) return;
-    const int32_t I = c_sell_row[pos];
-    if (I >= nC) return;
-    const int32_t b0 = bq * NS;
-    float Cm[NS][3][3] = {};
-    const int32_t g0 = gptr[pos], g1 = gptr[pos + 1];
-    if (g0 == g1 && pos != c_diag[I]) return;  // a lower block (its upper twin writes it, st_pair) or padding
-    for (int32_t g = g0; g < g1; ++g) {
-        const int32_t fp = gent[3 * g], ii = gent[3 * g + 1], jj = gent[3 * g + 2];
-        float qi[3][3], qj[3][3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                qi[k][c] = Q[((int64_t)ii * 3 + k) * 3 + c];
-                qj[k][c] = Q[((int64_t)jj * 3 + k) * 3 + c];
-            }
-        float a[NS][3][3];
-#pragma unroll
-        for (int t = 0; t < NS; ++t) {
-            ldm<3>(Af + (int64_t)min(b0 + t, B - 1) * f_sell_nb * kB3, max(fp, 0), a[t]);
-            if (fp < 0) {
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) a[t][r][k] = (fp == -1 && r == k) ? 1.f : 0.f;
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < NS; ++t) {
-            float T[3][3];  // A Q_j
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    float sum = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) sum += a[t][r][k] * qj[k][c];
-                    T[r][c] = sum;
-                }
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    float sum = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) sum += qi[k][r] * T[k][c];
-                    Cm[t][r][c] += sum;
-                }
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < NS; ++t) {
-        const int32_t b = b0 + t;
-        if (b >= B) continue;
-        if (pos == c_diag[I]) {
-#pragma unroll
-            for (int d = 0; d < 3; ++d)
-                if (c_dead[3 * (int64_t)I + d]) Cm[t][d][d] += 1.f;
-            sym3(Cm[t]);
-            float D[3][3];
-            inv3(Cm[t], D);
-            st_h9(Dh, Dh22, (int64_t)b * nC + I, D);
-        }
-        st_pair(Ac, Ah, Ah22, b, c_sell_nb, pos, c_twin[pos], Cm[t]);
-    }
-}
-
-// Levels >= 1 by gather entry (k_galerkin0_ent's scheme for the fp32 3x3
-// blocks): one entry of kGalENS systems per thread, its terms staged in LDS,
-// one thread per (coarse position, system) summing them in list order -- the
-// same bits as k_galerkin3_ns.
-__global__ __launch_bounds__(kWG) void k_galerkin3_ent(
-    int32_t ngrp, const int32_t *__restrict__ ggrp, int32_t nC, int32_t B, const int32_t *__restrict__ c_sell_row,
-    const int32_t *__restrict__ c_diag, const uint8_t *__restrict__ c_dead, const int32_t *__restrict__ c_twin, const int32_t *__restrict__ gptr,
-    const int32_t *__restrict__ gent, const float *__restrict__ Q, const float *__restrict__ Af, int64_t f_sell_nb,
-    int64_t c_sell_nb, float *__restrict__ Ac, uint4 *__restrict__ Dh, uint16_t *__restrict__ Dh22,
-    uint4 *__restrict__ Ah, uint16_t *__restrict__ Ah22) {
-#pragma clang fp contract(off)
-    __shared__ float con[kGalENS][9][kWG];
-    int32_t g, bq;
-    const int32_t nq = (B + kGalENS - 1) / kGalENS;
-    if (!xcd_map(ngrp, nq, g, bq, kGrpGal)) return;
-    const int32_t b0 = bq * kGalENS;
-    const int32_t p0 = ggrp[2 * g], p1 = ggrp[2 * g + 1];
-    const int32_t e0 = gptr[p0], e1 = gptr[p1];
-    const int32_t e = e0 + (int32_t)threadIdx.x;
-    const int32_t np = p1 - p0;
-    int32_t tI = nC, tq0 = 0, tq1 = 0, tdg = -1;
-    if ((int32_t)threadIdx.x < np * kGalENS) {
-        const int32_t pos = p0 + (int32_t)threadIdx.x / kGalENS;
-        tI = c_sell_row[pos];
-        tq0 = gptr[pos];
-        tq1 = gptr[pos + 1];
-        if (tI < nC) tdg = c_diag[tI];
-    }
-    if (e < e1) {
-        const int32_t fp = gent[3 * (int64_t)e], ii = gent[3 * (int64_t)e + 1], jj = gent[3 * (int64_t)e + 2];
-        float qi[3][3], qj[3][3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                qi[k][c] = Q[((int64_t)ii * 3 + k) * 3 + c];
-                qj[k][c] = Q[((int64_t)jj * 3 + k) * 3 + c];
-            }
-        float a[kGalENS][3][3];
-#pragma unroll
-        for (int t = 0; t < kGalENS; ++t) {
-            ldm<3>(Af + (int64_t)min(b0 + t, B - 1) * f_sell_nb * kB3, max(fp, 0), a[t]);
-            if (fp < 0) {
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) a[t][r][k] = (fp == -1 && r == k) ? 1.f : 0.f;
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < kGalENS; ++t) {
-            float T[3][3];  // A Q_j
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    float sum = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) sum += a[t][r][k] * qj[k][c];
-                    T[r][c] = sum;
-                }
-#pragma unroll
-            for (int r = 0; r < 3; ++r)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    float sum = 0.f;
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) sum += qi[k][r] * T[k][c];
-                    con[t][3 * r + c][threadIdx.x] = sum;
-                }
-        }
-    }
-    __syncthreads();
-    for (int32_t task = threadIdx.x; task < np * kGalENS; task += kWG) {
-        const int32_t pos = p0 + task / kGalENS, t = task % kGalENS, b = b0 + t;
-        const bool first = task == (int32_t)threadIdx.x;
-        const int32_t I = first ? tI : c_sell_row[pos];
-        if (I >= nC || b >= B) continue;
-        float Cm[3][3] = {};
-        const int32_t q0 = first ? tq0 : gptr[pos], q1 = first ? tq1 : gptr[pos + 1];
-        const bool diag = pos == (first ? tdg : c_diag[I]);
-        if (q0 == q1 && !diag) continue;  // a lower block (its upper twin writes it, st_pair) or padding
-        for (int32_t q = q0; q < q1; ++q)
-#pragma unroll
-            for (int k = 0; k < 9; ++k) Cm[k / 3][k % 3] += con[t][k][q - e0];
-        if (diag) {
-#pragma unroll
-            for (int d = 0; d < 3; ++d)
-                if (c_dead[3 * (int64_t)I + d]) Cm[d][d] += 1.f;
-            sym3(Cm);
-            float D[3][3];
-            inv3(Cm, D);
-            st_h9(Dh, Dh22, (int64_t)b * nC + I, D);
-        }
-        st_pair(Ac, Ah, Ah22, b, c_sell_nb, pos, c_twin[pos], Cm);
     }
 }
 
@@ -812,74 +635,42 @@ __global__ __launch_bounds__(kWG) void k_galerkin3_ent(
 // walks the list in chunks of kWG entries -- every thread one entry's term
 // for the NSB systems, staged in LDS -- and 9 NSB threads, one per (system,
 // block entry), fold each chunk in list order. Each block entry is a sum of
-// its own terms, so the bits are k_galerkin3_ns's. S1 (1536 systems), level
+// its own terms, so the bits are k_galerkin_ns's. S1 (1536 systems), level
 // 1 -> 2: 42.8 ms per launch per position -> 20.9 by chunk (and 4.6 ms for
 // the positions below the bound by entry); 4 systems per workgroup 23.1, 8
 // 25.8, bound 64 entries 24.9 + 3.3 (profiles/r05_ab/gal_slab/).
 constexpr int kGalBig = 128;
+constexpr int kGalBigNS = 2;
 template <int NSB>
-__global__ __launch_bounds__(kWG) void k_galerkin3_big(
-    int32_t nbig, const int32_t *__restrict__ gbig, int32_t nC, int32_t B, const int32_t *__restrict__ c_sell_row,
-    const int32_t *__restrict__ c_diag, const uint8_t *__restrict__ c_dead, const int32_t *__restrict__ c_twin, const int32_t *__restrict__ gptr,
-    const int32_t *__restrict__ gent, const float *__restrict__ Q, const float *__restrict__ Af, int64_t f_sell_nb,
-    int64_t c_sell_nb, float *__restrict__ Ac, uint4 *__restrict__ Dh, uint16_t *__restrict__ Dh22,
-    uint4 *__restrict__ Ah, uint16_t *__restrict__ Ah22) {
+__global__ __launch_bounds__(kWG) void k_galerkin3_big(GalArgs g, int32_t nbig, const int32_t *__restrict__ gbig,
+                                                       const float *__restrict__ Af, int64_t f_sell_nb) {
 #pragma clang fp contract(off)
     // rows padded by one word: the 9 NSB summing lanes read one column at
     // a time, kWG + 1 words apart -- distinct banks
     __shared__ float con[NSB][9][kWG + 1];
     __shared__ float fin[NSB][9];
-    int32_t g, bq;
-    if (!xcd_map(nbig, (B + NSB - 1) / NSB, g, bq, kGrpGal)) return;
+    int32_t grp, bq;
+    if (!xcd_map(nbig, (g.B + NSB - 1) / NSB, grp, bq, kGrpGal)) return;
     const int32_t b0 = bq * NSB;
-    const int32_t pos = gbig[g];
-    const int32_t e0 = gptr[pos], e1 = gptr[pos + 1];
+    const int32_t pos = gbig[grp];
+    const int32_t e0 = g.gptr[pos], e1 = g.gptr[pos + 1];
     const int32_t sk = (int32_t)threadIdx.x;  // summing lane: system sk / 9, block entry sk % 9
     float acc = 0.f;
     for (int32_t c0 = e0; c0 < e1; c0 += kWG) {
-        const int32_t e = c0 + (int32_t)threadIdx.x;
+        const int64_t e = c0 + (int32_t)threadIdx.x;
         if (e < e1) {
-            const int32_t fp = gent[3 * (int64_t)e], ii = gent[3 * (int64_t)e + 1], jj = gent[3 * (int64_t)e + 2];
-            float qi[3][3], qj[3][3];
+            const int32_t fp = g.gent[3 * e], ii = g.gent[3 * e + 1], jj = g.gent[3 * e + 2];
+            float qi[9], qj[9], a[NSB][3][3];
+            ld_p<3>(g.Q, ii, qi);
+            ld_p<3>(g.Q, jj, qj);
 #pragma unroll
-            for (int k = 0; k < 3; ++k)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    qi[k][c] = Q[((int64_t)ii * 3 + k) * 3 + c];
-                    qj[k][c] = Q[((int64_t)jj * 3 + k) * 3 + c];
-                }
-            float a[NSB][3][3];
+            for (int t = 0; t < NSB; ++t) ld_fine<3>(Af, (int64_t)min(b0 + t, g.B - 1) * f_sell_nb, 1, fp, a[t]);
 #pragma unroll
             for (int t = 0; t < NSB; ++t) {
-                ldm<3>(Af + (int64_t)min(b0 + t, B - 1) * f_sell_nb * kB3, max(fp, 0), a[t]);
-                if (fp < 0) {
+                float T[3][3];
+                gal_term<3>(a[t], qi, qj, T);
 #pragma unroll
-                    for (int r = 0; r < 3; ++r)
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) a[t][r][k] = (fp == -1 && r == k) ? 1.f : 0.f;
-                }
-            }
-#pragma unroll
-            for (int t = 0; t < NSB; ++t) {
-                float T[3][3];  // A Q_j
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        float sum = 0.f;
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) sum += a[t][r][k] * qj[k][c];
-                        T[r][c] = sum;
-                    }
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        float sum = 0.f;
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) sum += qi[k][r] * T[k][c];
-                        con[t][3 * r + c][threadIdx.x] = sum;
-                    }
+                for (int k = 0; k < 9; ++k) con[t][k][threadIdx.x] = T[k / 3][k % 3];
             }
         }
         __syncthreads();
@@ -902,23 +693,14 @@ __global__ __launch_bounds__(kWG) void k_galerkin3_big(
     __syncthreads();
     if ((int32_t)threadIdx.x >= NSB) return;
     const int32_t t = (int32_t)threadIdx.x, b = b0 + t;
-    if (b >= B) return;
-    const int32_t I = c_sell_row[pos];
+    if (b >= g.B) return;
+    const int32_t I = g.sell_row[pos];
     float Cm[3][3];
 #pragma unroll
     for (int k = 0; k < 9; ++k) Cm[k / 3][k % 3] = fin[t][k];
-    if (pos == c_diag[I]) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d)
-            if (c_dead[3 * (int64_t)I + d]) Cm[d][d] += 1.f;
-        sym3(Cm);
-        float D[3][3];
-        inv3(Cm, D);
-        st_h9(Dh, Dh22, (int64_t)b * nC + I, D);
-    }
-    st_pair(Ac, Ah, Ah22, b, c_sell_nb, pos, c_twin[pos], Cm);
+    gal_finish(g, b, pos, I, pos == g.diag[I], Cm);
 }
-constexpr int kGalBigNS = 2;
+
 
 constexpr int kMaxCoarse = 128;
 constexpr int kInvWG = 1024;
@@ -1896,14 +1678,13 @@ void launch_bsweep(const AmgDevice &G, SysMap sm, const float *rv, float *xv, fl
     k_bsweep<F32X><<<dim3((unsigned)sm.n), kBswWG, lds, s>>>(bsw_args(G), sm, rv, xv, omega, G.bsw_sweeps, sysi);
 }
 
-template <int XM, bool ZH, typename... Args>
-void launch_post0(bool packed, int32_t nblk, int32_t B, hipStream_t s, Args... args) {
+template <int XM, typename... Args>
+void launch_post0(bool zh, bool packed, int32_t nblk, int32_t B, hipStream_t s, Args... args) {
     const dim3 g(xcd_grid(nblk, (B + kPost0NS - 1) / kPost0NS, kGrpSmooth > kPost0NS ? kGrpSmooth / kPost0NS : 1));
-    ++g_vcycle_launches[kVcPost0 + (XM - 1) * 4 + (ZH ? 2 : 0) + (packed ? 1 : 0)];
-    if (packed)
-        k_post0_ns<XM, ZH, kPost0NS, true><<<g, kWG, 0, s>>>(args...);
-    else
-        k_post0_ns<XM, ZH, kPost0NS, false><<<g, kWG, 0, s>>>(args...);
+    ++g_vcycle_launches[kVcPost0 + (XM - 1) * 4 + (zh ? 2 : 0) + (packed ? 1 : 0)];
+    (zh ? (packed ? k_post0_ns<XM, true, kPost0NS, true> : k_post0_ns<XM, true, kPost0NS, false>)
+        : (packed ? k_post0_ns<XM, false, kPost0NS, true> : k_post0_ns<XM, false, kPost0NS, false>))
+        <<<g, kWG, 0, s>>>(args...);
 }
 
 inline dim3 grid2(int64_t n, int32_t B) { return dim3((unsigned)((n + kWG - 1) / kWG), (unsigned)B); }
@@ -2272,7 +2053,7 @@ bool amg_build(mof_mesh *m) {
             }
             // tentative P (every level but a smoothed level 0): coarse position
             // ranges of <= kWG gather entries and positions for the products by
-            // entry, k_galerkin0_ent / k_galerkin3_ent (unless a level-0
+            // entry, k_galerkin_ent<2> / k_galerkin_ent<3> (unless a level-0
             // position has more). Levels >= 1: positions past kGalBig entries
             // go to k_galerkin3_big.
             if (!L.smoothed || l >= 1) {
@@ -2386,9 +2167,27 @@ AmgFine amg_fine(mof_mesh *m) {
     return f;
 }
 
-static uint4 *ah(AmgDevLevel &C) { return C.Ah.n > 1 ? reinterpret_cast<uint4 *>(C.Ah.p) : nullptr; }
-static uint16_t *ah22(AmgDevLevel &C) { return C.Ah22.n > 1 ? C.Ah22.p : nullptr; }
-static uint4 *dh(AmgDevLevel &C) { return reinterpret_cast<uint4 *>(C.Dh.p); }
+// the product of level F into level C for a batch of B systems (a sweep copy
+// only where C keeps one: every level but the coarsest)
+static GalArgs gal_args(const AmgDevLevel &F, const AmgDevLevel &C, int32_t B) {
+    GalArgs g;
+    g.c_sell_nb = C.sell_nb;
+    g.nC = C.n;
+    g.B = B;
+    g.sell_row = C.sell_row.p;
+    g.diag = C.diag_pos.p;
+    g.dead = C.dead.p;
+    g.twin = C.twin.p;
+    g.gptr = F.gptr.p;
+    g.gent = F.gent.p;
+    g.Q = F.Q.p;
+    g.Ac = C.A.p;
+    g.Dh = reinterpret_cast<uint4 *>(C.Dh.p);
+    g.Dh22 = C.Dh22.p;
+    g.Ah = C.Ah.n > 1 ? reinterpret_cast<uint4 *>(C.Ah.p) : nullptr;
+    g.Ah22 = C.Ah22.n > 1 ? C.Ah22.p : nullptr;
+    return g;
+}
 
 void amg_setup_batch(mof_mesh *m, int32_t B, hipStream_t s) {
     AmgDevice &G = *m->amg;
@@ -2418,89 +2217,75 @@ void amg_setup_batch(mof_mesh *m, int32_t B, hipStream_t s) {
     // terms in the same order, bit-identical (round 4: an unsliced by-entry
     // launch past the bound skipped workgroups)
     auto fits = [&](int32_t nblk, int32_t ns) {
-        const int64_t nq = (B + ns - 1) / ns, G = sys_group((int32_t)nq, kGrpGal);
-        return 8 * G * ((nq + G - 1) / G) * ((nblk + 7) / 8) * kWG < ((int64_t)1 << 32);
+        const int64_t nq = (B + ns - 1) / ns, sg = sys_group((int32_t)nq, kGrpGal);
+        return 8 * sg * ((nq + sg - 1) / sg) * ((nblk + 7) / 8) * kWG < ((int64_t)1 << 32);
     };
     auto ent_fits = [&](const AmgDevLevel &F) {
         return !g_force_galerkin_ns.load() && (F.nggrp > 0 || F.nbig > 0) && fits(F.nggrp, kGalENS) &&
                fits(F.nbig, kGalBigNS);
     };
+    // nblk workgroups for each ns systems of the batch
+    auto gal_grid = [&](int64_t nblk, int32_t ns) { return dim3(xcd_grid((int32_t)nblk, (B + ns - 1) / ns, kGrpGal)); };
+    const int64_t fnb = m->pat.sell_nb();
+    const uint2 *A0h = reinterpret_cast<const uint2 *>(G.A0h.p);
     // a smoothed level 0: its product, and level 1's when level 1 kept a
     // slab copy, by system slab (k_a_slab -> k_galerkin_sys<2> -> <3>)
     size_t l_first = 0;
     if (G.lv[0].smoothed && G.aslab.n > 0) {
-        AmgDevLevel &F = G.lv[0], &C = G.lv[1];
+        AmgDevLevel &C = G.lv[1];
         const bool l1 = L >= 3 && C.slab.n > 0;
-        const int64_t fnb = m->pat.sell_nb();
+        const GalArgs g0 = gal_args(G.lv[0], C, B), g1 = l1 ? gal_args(C, G.lv[2], B) : GalArgs{};
         auto sys_grid = [](int64_t nb) { return dim3(xcd_grid((int32_t)((nb + kGalSysPos - 1) / kGalSysPos), 1, 1)); };
+        const dim3 gs((unsigned)((fnb + kSlabPos - 1) / kSlabPos));
+        auto *cs = l1 ? reinterpret_cast<float4 *>(C.slab.p) : nullptr;
         for (int32_t b0 = 0; b0 < B; b0 += kSlab) {
-            const dim3 gs((unsigned)((fnb + kSlabPos - 1) / kSlabPos));
-            if (G.regular)
-                k_a_slab<uint2><<<gs, kWG, 0, s>>>(fnb, b0, std::min(kSlab, B - b0),
-                                                   reinterpret_cast<const uint2 *>(G.A0h.p),
-                                                   reinterpret_cast<uint2 *>(G.aslab.p));
-            else
-                k_a_slab<float4><<<gs, kWG, 0, s>>>(fnb, b0, std::min(kSlab, B - b0),
-                                                    reinterpret_cast<const float4 *>(w.A32.p),
-                                                    reinterpret_cast<float4 *>(G.aslab.p));
-            auto *cs = l1 ? reinterpret_cast<float4 *>(C.slab.p) : nullptr;
-            ++g_galerkin_launches[G.regular ? kGalSys2Bf16 : kGalSys2F32];
-            if (G.regular)
-                k_galerkin_sys<2, true><<<sys_grid(C.sell_nb), kWG, 0, s>>>(
-                    C.sell_nb, C.n, B, b0, C.sell_row.p, C.diag_pos.p, C.dead.p, C.twin.p, F.gptr.p, F.gent.p, F.Q.p,
-                    reinterpret_cast<const float4 *>(G.aslab.p), C.A.p, dh(C), C.Dh22.p, ah(C), ah22(C), cs);
-            else
-                k_galerkin_sys<2><<<sys_grid(C.sell_nb), kWG, 0, s>>>(
-                    C.sell_nb, C.n, B, b0, C.sell_row.p, C.diag_pos.p, C.dead.p, C.twin.p, F.gptr.p, F.gent.p, F.Q.p,
-                    reinterpret_cast<const float4 *>(G.aslab.p), C.A.p, dh(C), C.Dh22.p, ah(C), ah22(C), cs);
+            const int32_t nb = std::min(kSlab, B - b0);
+            if (G.regular) {
+                auto *slab = reinterpret_cast<uint2 *>(G.aslab.p);
+                k_a_slab<uint2><<<gs, kWG, 0, s>>>(fnb, b0, nb, A0h, slab);
+                ++g_galerkin_launches[kGalSys2Bf16];
+                k_galerkin_sys<2, true><<<sys_grid(g0.c_sell_nb), kWG, 0, s>>>(g0, slab, b0, cs);
+            } else {
+                auto *slab = reinterpret_cast<float4 *>(G.aslab.p);
+                k_a_slab<float4><<<gs, kWG, 0, s>>>(fnb, b0, nb, reinterpret_cast<const float4 *>(w.A32.p), slab);
+                ++g_galerkin_launches[kGalSys2F32];
+                k_galerkin_sys<2><<<sys_grid(g0.c_sell_nb), kWG, 0, s>>>(g0, slab, b0, cs);
+            }
             if (l1) {
-                AmgDevLevel &C2 = G.lv[2];
                 ++g_galerkin_launches[kGalSys3];
-                k_galerkin_sys<3><<<sys_grid(C2.sell_nb), kWG, 0, s>>>(
-                    C2.sell_nb, C2.n, B, b0, C2.sell_row.p, C2.diag_pos.p, C2.dead.p, C2.twin.p, C.gptr.p, C.gent.p, C.Q.p,
-                    reinterpret_cast<const float4 *>(C.slab.p), C2.A.p, dh(C2), C2.Dh22.p, ah(C2), ah22(C2), nullptr);
+                k_galerkin_sys<3><<<sys_grid(g1.c_sell_nb), kWG, 0, s>>>(g1, C.slab.p, b0, nullptr);
             }
         }
         l_first = l1 ? 2 : 1;
     }
+    // the other levels: by gather entry where the lists allow it (ent_fits),
+    // else per position
     for (size_t l = l_first; l + 1 < L; ++l) {
         AmgDevLevel &F = G.lv[l], &C = G.lv[l + 1];
+        const GalArgs g = gal_args(F, C, B);
         const bool ent = ent_fits(F);
-        // the launch counters of the branches below (mof_test_galerkin_launches)
-        if (l == 0) {
-            ++g_galerkin_launches[ent ? kGal0Ent : kGal0Ns];
+        if (l == 0 && ent) {
+            ++g_galerkin_launches[kGal0Ent];
+            k_galerkin_ent<2><<<gal_grid(F.nggrp, kGalENS), kWG, 0, s>>>(g, F.nggrp, F.ggrp.p, A0h, fnb);
+        } else if (l == 0) {
+            ++g_galerkin_launches[kGal0Ns];
+            k_galerkin_ns<2, kGalNS><<<gal_grid((C.sell_nb + kWG - 1) / kWG, kGalNS), kWG, 0, s>>>(
+                g, w.A32.p, fnb, F.smoothed ? nullptr : A0h);
         } else if (ent) {
-            if (F.nggrp > 0) ++g_galerkin_launches[kGal3Ent];
-            if (F.nbig > 0) ++g_galerkin_launches[kGal3Big];
+            if (F.nggrp > 0) {
+                ++g_galerkin_launches[kGal3Ent];
+                k_galerkin_ent<3><<<gal_grid(F.nggrp, kGalENS), kWG, 0, s>>>(g, F.nggrp, F.ggrp.p, F.A.p, F.sell_nb);
+            }
+            if (F.nbig > 0) {
+                ++g_galerkin_launches[kGal3Big];
+                k_galerkin3_big<kGalBigNS><<<gal_grid(F.nbig, kGalBigNS), kWG, 0, s>>>(g, F.nbig, F.gbig.p, F.A.p,
+                                                                                      F.sell_nb);
+            }
         } else {
             ++g_galerkin_launches[kGal3Ns];
+            k_galerkin_ns<3, kGal3NS><<<gal_grid((C.sell_nb + kWG - 1) / kWG, kGal3NS), kWG, 0, s>>>(
+                g, F.A.p, F.sell_nb, nullptr);
         }
-        if (l == 0 && ent)
-            k_galerkin0_ent<<<dim3(xcd_grid(F.nggrp, (B + kGalENS - 1) / kGalENS, kGrpGal)), kWG, 0, s>>>(
-                F.nggrp, F.ggrp.p, C.n, B, C.sell_row.p, C.diag_pos.p, C.dead.p, C.twin.p, F.gptr.p, F.gent.p, F.Q.p,
-                reinterpret_cast<const uint2 *>(G.A0h.p), m->pat.sell_nb(), C.sell_nb, C.A.p, dh(C), C.Dh22.p, ah(C),
-                ah22(C));
-        else if (l == 0)
-            k_galerkin0_ns<<<dim3(xcd_grid((int32_t)((C.sell_nb + kWG - 1) / kWG), (B + kGalNS - 1) / kGalNS,
-                                           kGrpGal)),
-                             kWG, 0, s>>>(C.sell_nb, C.n, B, C.sell_row.p, C.diag_pos.p, C.dead.p, C.twin.p, F.gptr.p, F.gent.p,
-                                          F.Q.p, w.A32.p, m->pat.sell_nb(), C.A.p, dh(C), C.Dh22.p, ah(C), ah22(C),
-                                          F.smoothed ? nullptr : reinterpret_cast<const uint2 *>(G.A0h.p));
-        else if (ent) {
-            if (F.nggrp > 0)
-                k_galerkin3_ent<<<dim3(xcd_grid(F.nggrp, (B + kGalENS - 1) / kGalENS, kGrpGal)), kWG, 0, s>>>(
-                    F.nggrp, F.ggrp.p, C.n, B, C.sell_row.p, C.diag_pos.p, C.dead.p, C.twin.p, F.gptr.p, F.gent.p, F.Q.p, F.A.p,
-                    F.sell_nb, C.sell_nb, C.A.p, dh(C), C.Dh22.p, ah(C), ah22(C));
-            if (F.nbig > 0)
-                k_galerkin3_big<kGalBigNS>
-                    <<<dim3(xcd_grid(F.nbig, (B + kGalBigNS - 1) / kGalBigNS, kGrpGal)), kWG, 0, s>>>(
-                        F.nbig, F.gbig.p, C.n, B, C.sell_row.p, C.diag_pos.p, C.dead.p, C.twin.p, F.gptr.p, F.gent.p, F.Q.p,
-                        F.A.p, F.sell_nb, C.sell_nb, C.A.p, dh(C), C.Dh22.p, ah(C), ah22(C));
-        } else
-            k_galerkin3_ns<kGal3NS>
-                <<<dim3(xcd_grid((int32_t)((C.sell_nb + kWG - 1) / kWG), (B + kGal3NS - 1) / kGal3NS, kGrpGal)), kWG,
-                   0, s>>>(C.sell_nb, C.n, B, C.sell_row.p, C.diag_pos.p, C.dead.p, C.twin.p, F.gptr.p, F.gent.p, F.Q.p, F.A.p,
-                           F.sell_nb, C.A.p, dh(C), C.Dh22.p, ah(C), ah22(C));
     }
     AmgDevLevel &Lc = G.lv[L - 1];
     k_coarse_inverse<<<dim3((unsigned)B), kInvWG, 0, s>>>(Lc.n, Lc.sell_off.p, Lc.sell_col.p, Lc.A.p,
@@ -2567,68 +2352,10 @@ void amg_vcycle(mof_mesh *m, int32_t B, const float *r0, float *z0, double *part
                                hipMemcpyDeviceToDevice, s));
     };
     tap_x(0, v[0].x, 1);
-    // the cycle below level 0 from level 1's restricted b and pre-smoothed
-    // x: down (residual, restriction + next pre-smooth), the fused tiny
-    // levels, up (prolongation, post-smoothing into y)
-    auto coarse = [&](Lvl (&u)[kMaxLevels]) {
-        for (int32_t l = 1; l < S; ++l) {
-            const int32_t smooth = l + 1 < L - 1;
-            k_res3<<<grid2(u[l].n, nL), kWG, 0, s>>>(u[l], sysi);
-            ++g_vcycle_launches[kVcRes3];
-            ++g_vcycle_launches[G.lv[l].smoothed ? kVcRestrict0Sa3 : kVcRestrict3];
-            if (G.lv[l].smoothed)
-                k_restrict0_sa<3><<<dim3(xcd_grid(G.lv[l].ngrp, (nL + kNSR - 1) / kNSR, kGrpRestr)), kWG, 0, s>>>(
-                    u[l], u[l + 1], G.lv[l].rgrp.p, G.lv[l].ngrp, B, smooth, om1, sysi);
-            else
-                k_restrict<3><<<dim3(xcd_grid(G.lv[l].ngrp, nL, kGrpRestr)), kWG, 0, s>>>(
-                    u[l], u[l + 1], G.lv[l].rgrp.p, G.lv[l].ngrp, B, smooth, om1, sysi);
-        }
+    // the fused tiny levels first .. L - 1 and the coarsest solve
+    auto subcycle = [&](int32_t first) {
         SubArgs sa;
-        sa.first = S;
-        sa.last = L - 1;
-        for (int32_t l = 0; l < L; ++l) sa.lv[l] = u[l];
-        sa.cinv = G.cinv.p;
-        sa.omega = om1;
-        sa.sysi = sysi;
-        k_subcycle<<<dim3((unsigned)nL), kSubWG, 0, s>>>(sa);
-        ++g_vcycle_launches[kVcSubcycle];
-        for (int32_t l = S - 1; l >= 1; --l) {
-            ++g_vcycle_launches[G.lv[l].smoothed ? kVcProlong3Sa : kVcProlong3];
-            ++g_vcycle_launches[kVcPost3];
-            if (G.lv[l].smoothed) {
-                const int32_t nb = (u[l].n + kWG - 1) / kWG;
-                k_prolong3_sa<<<dim3(xcd_grid(nb, (nL + kNS3 - 1) / kNS3, kGrpProl)), kWG, 0, s>>>(u[l], u[l + 1], nb,
-                                                                                                   B, sysi);
-            }
-            else
-                k_prolong<3><<<grid2(u[l].n, nL), kWG, 0, s>>>(u[l], u[l + 1], sysi);
-            k_post3<<<grid2(u[l].n, nL), kWG, 0, s>>>(u[l], om1, sysi);
-        }
-    };
-    // down at level 0: residual of the pre-smoothed x, restriction (+ level
-    // 1's pre-smooth)
-    for (int32_t l = 0; l < 1; ++l) {
-        const int32_t smooth = l + 1 < L - 1;
-        if (l == 0) {
-            if (G.bsw_n > 0) launch_bsweep<false>(G, sm, r0, v[0].x, om, sysi, s);
-            tap_x(1, v[0].x, 1);
-            ++g_vcycle_launches[mat0.sell_idx ? kVcRes0Pk : kVcRes0];
-            ++g_vcycle_launches[G.lv[0].smoothed ? kVcRestrict0Sa2 : kVcRestrict2];
-            const dim3 gr(xcd_grid(nblk, (nL + kRes0NS - 1) / kRes0NS, kGrpSmooth > kRes0NS ? kGrpSmooth / kRes0NS : 1));
-            (mat0.sell_idx ? k_res0_ns<kRes0NS, true> : k_res0_ns<kRes0NS, false>)<<<gr, kWG, 0, s>>>(
-                v[0].n, nblk, B, sm, mat0, r0, v[0].x, G.lv[0].smoothed ? nullptr : v[0].apos, sysi, v[0].r);
-            if (G.lv[0].smoothed) {
-                k_restrict0_sa<2><<<dim3(xcd_grid(G.lv[0].ngrp, (nL + kNSR - 1) / kNSR, kGrpRestr)), kWG, 0, s>>>(
-                    v[0], v[1], G.lv[0].rgrp.p, G.lv[0].ngrp, B, smooth, om1, sysi);
-            } else {
-                k_restrict<2, kRestrS><<<dim3(xcd_grid(G.lv[0].ngrp, (nL + kRestrS - 1) / kRestrS, kGrpRestr)), kWG, 0, s>>>(
-                    v[0], v[1], G.lv[0].rgrp.p, G.lv[0].ngrp, B, smooth, om1, sysi);
-            }
-        }
-    }
-    if (S == 1) {  // level 1 is already one of the fused tiny levels
-        SubArgs sa;
-        sa.first = 1;
+        sa.first = first;
         sa.last = L - 1;
         for (int32_t l = 0; l < L; ++l) sa.lv[l] = v[l];
         sa.cinv = G.cinv.p;
@@ -2636,41 +2363,85 @@ void amg_vcycle(mof_mesh *m, int32_t B, const float *r0, float *z0, double *part
         sa.sysi = sysi;
         k_subcycle<<<dim3((unsigned)nL), kSubWG, 0, s>>>(sa);
         ++g_vcycle_launches[kVcSubcycle];
-    } else {
-        coarse(v);
-    }
-    // up at level 0: coarse correction, post-smooth
-    for (int32_t l = 0; l >= 0; --l) {
-        if (l == 0) {
-            const int32_t nb0 = (v[0].n + kWG - 1) / kWG;
-            const int32_t nb0p = (v[0].n + kWG * kProlR - 1) / (kWG * kProlR);
-            const dim3 gsa(xcd_grid(nb0, (nL + kNSP - 1) / kNSP, kGrpProl)), gp(xcd_grid(nb0p, (nL + kProlS - 1) / kProlS, kGrpProl));
-            ++g_vcycle_launches[(G.lv[0].smoothed ? kVcProlong0SaX1 : kVcProlong0X1) + (G.xm == 2 ? 1 : 0)];
-            if (G.xm == 2) {
-                if (G.lv[0].smoothed)
-                    k_prolong0_sa<2><<<gsa, kWG, 0, s>>>(v[0], v[1], nb0, B, sysi);
-                else
-                    k_prolong0<2><<<gp, kWG, 0, s>>>(v[0], v[1], nb0p, B, sysi);
-                tap_x(2, v[0].y, 2);
-                if (G.bsw_n > 0) launch_bsweep<true>(G, sm, r0, v[0].y, om, sysi, s);
-                tap_x(3, v[0].y, 2);
-                if (zh)
-                    launch_post0<2, true>(mat0.sell_idx != nullptr, nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, v[0].y, om, sysi, z0, part_slot, rd);
-                else
-                    launch_post0<2, false>(mat0.sell_idx != nullptr, nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, v[0].y, om, sysi, z0, part_slot, rd);
-            } else {
-                if (G.lv[0].smoothed)
-                    k_prolong0_sa<1><<<gsa, kWG, 0, s>>>(v[0], v[1], nb0, B, sysi);
-                else
-                    k_prolong0<1><<<gp, kWG, 0, s>>>(v[0], v[1], nb0p, B, sysi);
-                tap_x(2, v[0].x, 1);
-                if (G.bsw_n > 0) launch_bsweep<false>(G, sm, r0, v[0].x, om, sysi, s);
-                tap_x(3, v[0].x, 1);
-                if (zh)
-                    launch_post0<1, true>(mat0.sell_idx != nullptr, nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, v[0].x, om, sysi, z0, part_slot, rd);
-                else
-                    launch_post0<1, false>(mat0.sell_idx != nullptr, nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, v[0].x, om, sysi, z0, part_slot, rd);
+    };
+    // the cycle below level 0 from level 1's restricted b and pre-smoothed
+    // x: down (residual, restriction + next pre-smooth), the fused tiny
+    // levels, up (prolongation, post-smoothing into y)
+    auto coarse = [&]() {
+        for (int32_t l = 1; l < S; ++l) {
+            const int32_t smooth = l + 1 < L - 1;
+            k_res3<<<grid2(v[l].n, nL), kWG, 0, s>>>(v[l], sysi);
+            ++g_vcycle_launches[kVcRes3];
+            ++g_vcycle_launches[G.lv[l].smoothed ? kVcRestrict0Sa3 : kVcRestrict3];
+            if (G.lv[l].smoothed)
+                k_restrict0_sa<3><<<dim3(xcd_grid(G.lv[l].ngrp, (nL + kNSR - 1) / kNSR, kGrpRestr)), kWG, 0, s>>>(
+                    v[l], v[l + 1], G.lv[l].rgrp.p, G.lv[l].ngrp, B, smooth, om1, sysi);
+            else
+                k_restrict<3><<<dim3(xcd_grid(G.lv[l].ngrp, nL, kGrpRestr)), kWG, 0, s>>>(
+                    v[l], v[l + 1], G.lv[l].rgrp.p, G.lv[l].ngrp, B, smooth, om1, sysi);
+        }
+        subcycle(S);
+        for (int32_t l = S - 1; l >= 1; --l) {
+            ++g_vcycle_launches[G.lv[l].smoothed ? kVcProlong3Sa : kVcProlong3];
+            ++g_vcycle_launches[kVcPost3];
+            if (G.lv[l].smoothed) {
+                const int32_t nb = (v[l].n + kWG - 1) / kWG;
+                k_prolong3_sa<<<dim3(xcd_grid(nb, (nL + kNS3 - 1) / kNS3, kGrpProl)), kWG, 0, s>>>(v[l], v[l + 1], nb,
+                                                                                                   B, sysi);
             }
+            else
+                k_prolong<3><<<grid2(v[l].n, nL), kWG, 0, s>>>(v[l], v[l + 1], sysi);
+            k_post3<<<grid2(v[l].n, nL), kWG, 0, s>>>(v[l], om1, sysi);
+        }
+    };
+    // down at level 0: residual of the pre-smoothed x, restriction (+ level
+    // 1's pre-smooth)
+    {
+        const int32_t smooth = 1 < L - 1;
+        if (G.bsw_n > 0) launch_bsweep<false>(G, sm, r0, v[0].x, om, sysi, s);
+        tap_x(1, v[0].x, 1);
+        ++g_vcycle_launches[mat0.sell_idx ? kVcRes0Pk : kVcRes0];
+        ++g_vcycle_launches[G.lv[0].smoothed ? kVcRestrict0Sa2 : kVcRestrict2];
+        const dim3 gr(xcd_grid(nblk, (nL + kRes0NS - 1) / kRes0NS, kGrpSmooth > kRes0NS ? kGrpSmooth / kRes0NS : 1));
+        (mat0.sell_idx ? k_res0_ns<kRes0NS, true> : k_res0_ns<kRes0NS, false>)<<<gr, kWG, 0, s>>>(
+            v[0].n, nblk, B, sm, mat0, r0, v[0].x, G.lv[0].smoothed ? nullptr : v[0].apos, sysi, v[0].r);
+        if (G.lv[0].smoothed) {
+            k_restrict0_sa<2><<<dim3(xcd_grid(G.lv[0].ngrp, (nL + kNSR - 1) / kNSR, kGrpRestr)), kWG, 0, s>>>(
+                v[0], v[1], G.lv[0].rgrp.p, G.lv[0].ngrp, B, smooth, om1, sysi);
+        } else {
+            k_restrict<2, kRestrS><<<dim3(xcd_grid(G.lv[0].ngrp, (nL + kRestrS - 1) / kRestrS, kGrpRestr)), kWG, 0, s>>>(
+                v[0], v[1], G.lv[0].rgrp.p, G.lv[0].ngrp, B, smooth, om1, sysi);
+        }
+    }
+    if (S == 1)  // level 1 is already one of the fused tiny levels
+        subcycle(1);
+    else
+        coarse();
+    // up at level 0: coarse correction, post-smooth
+    {
+        const int32_t nb0 = (v[0].n + kWG - 1) / kWG;
+        const int32_t nb0p = (v[0].n + kWG * kProlR - 1) / (kWG * kProlR);
+        const dim3 gsa(xcd_grid(nb0, (nL + kNSP - 1) / kNSP, kGrpProl)), gp(xcd_grid(nb0p, (nL + kProlS - 1) / kProlS, kGrpProl));
+        const bool packed = mat0.sell_idx != nullptr;
+        ++g_vcycle_launches[(G.lv[0].smoothed ? kVcProlong0SaX1 : kVcProlong0X1) + (G.xm == 2 ? 1 : 0)];
+        if (G.xm == 2) {
+            if (G.lv[0].smoothed)
+                k_prolong0_sa<2><<<gsa, kWG, 0, s>>>(v[0], v[1], nb0, B, sysi);
+            else
+                k_prolong0<2><<<gp, kWG, 0, s>>>(v[0], v[1], nb0p, B, sysi);
+            tap_x(2, v[0].y, 2);
+            if (G.bsw_n > 0) launch_bsweep<true>(G, sm, r0, v[0].y, om, sysi, s);
+            tap_x(3, v[0].y, 2);
+            launch_post0<2>(zh, packed, nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, v[0].y, om, sysi, z0, part_slot, rd);
+        } else {
+            if (G.lv[0].smoothed)
+                k_prolong0_sa<1><<<gsa, kWG, 0, s>>>(v[0], v[1], nb0, B, sysi);
+            else
+                k_prolong0<1><<<gp, kWG, 0, s>>>(v[0], v[1], nb0p, B, sysi);
+            tap_x(2, v[0].x, 1);
+            if (G.bsw_n > 0) launch_bsweep<false>(G, sm, r0, v[0].x, om, sysi, s);
+            tap_x(3, v[0].x, 1);
+            launch_post0<1>(zh, packed, nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, v[0].x, om, sysi, z0, part_slot, rd);
         }
     }
     MOF_HIP(hipGetLastError());

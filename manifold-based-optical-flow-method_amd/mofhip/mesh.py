@@ -454,8 +454,8 @@ GALERKIN_KERNELS = ("galerkin0_ns", "galerkin0_ent", "galerkin_sys2_f32", "galer
 
 class force_galerkin_ns:
     """Tests only (mof_test_force_galerkin_ns): multigrid setups inside the
-    block take the per-position Galerkin products k_galerkin0_ns /
-    k_galerkin3_ns where the by-entry ones would run."""
+    block take the per-position Galerkin products k_galerkin_ns<2> /
+    k_galerkin_ns<3> where the by-entry ones would run."""
 
     def __enter__(self):
         L.check(L.lib().mof_test_force_galerkin_ns(1))

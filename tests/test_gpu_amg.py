@@ -240,7 +240,7 @@ def test_slab_galerkin_batch_split():
 
 @pytest.mark.parametrize("case", ["G1_ico642", "G2_cap641"])
 def test_galerkin_by_entry_batch_split(case):
-    """The level-0 Galerkin product by gather entry (k_galerkin0_ent, the
+    """The level-0 Galerkin product by gather entry (k_galerkin_ent<2>, the
     tentative prolongator's) puts two systems in a thread: the same bits for
     a batch split into partial system pairs (7) as for the whole batch, and
     V within 1e-6 of the reference's spsolve (golden V_k)."""
@@ -259,7 +259,7 @@ def test_galerkin_by_entry_batch_split(case):
 
 
 def test_coarse_galerkin_by_entry_batch_split():
-    """Levels >= 1 by gather entry (k_galerkin3_ent) and, for positions past
+    """Levels >= 1 by gather entry (k_galerkin_ent<3>) and, for positions past
     kGalBig entries, the chunked k_galerkin3_big, on a mesh with two coarse
     products (10,242 -> ~1.3k -> ~170 nodes): the same bits for ragged system
     groups (batch 7) as for the whole batch, V within 1e-6 of the oracle."""

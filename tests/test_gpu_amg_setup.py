@@ -14,9 +14,9 @@ contraction) from k scalar products a q q whose absolute values sum to S is
 within (k + 8) 2^-24 S of the exact sum in any order. Largest error / bound
 seen on an MI355X over the blocks each kernel computes (the diagonal and upper
 positions; test_galerkin_product prints them, -s):
-  k_galerkin0_ent 0.237   k_galerkin0_ns 0.237   k_galerkin_sys<2> fp32 0.281
-  k_galerkin_sys<2> bf16 0.217   k_galerkin_sys<3> 0.091   k_galerkin3_ent 0.125
-  k_galerkin3_ns 0.125   k_galerkin3_big 0.006
+  k_galerkin_ent<2> 0.237   k_galerkin_ns<2> 0.237   k_galerkin_sys<2> fp32 0.281
+  k_galerkin_sys<2> bf16 0.217   k_galerkin_sys<3> 0.091   k_galerkin_ent<3> 0.125
+  k_galerkin_ns<3> 0.125   k_galerkin3_big 0.006
 The lower twins meet the same bound with the same figures, and the coarsest
 inverse is within 0.79 .. 0.97 of its bound against numpy's. Both needed the
 operators symmetric to the bit (these tests caught it, hull3000 / hull_chain
@@ -28,7 +28,7 @@ coarsest inverse missed its by 10 .. 460 (a sweep that takes row k for column
 k, on a matrix symmetric only to fp32 rounding).
 
 icosphere(32, jitter=0.005) has no coarse gather list past kGalBig = 128 terms
-(the longest has 56: its two coarse products are all k_galerkin3_ent's, nbig = 0): k_galerkin3_big is
+(the longest has 56: its two coarse products are all k_galerkin_ent<3>'s, nbig = 0): k_galerkin3_big is
 checked where it does run -- G2_cap641, the smoothed G1_ico642, hull3000, S1s.
 """
 import functools
@@ -394,7 +394,7 @@ def test_coarsest_inverse_replays_sweep(case):
 
 @pytest.mark.parametrize("case", ["G1_ico642", "ico32"])
 def test_per_position_products_equal_by_entry(case):
-    """k_galerkin0_ns / k_galerkin3_ns (forced on a fresh handle) leave the
+    """k_galerkin_ns<2> / k_galerkin_ns<3> (forced on a fresh handle) leave the
     bytes of the by-entry kernels on every level: A, D^-1, the sweep copy and
     the coarsest inverse."""
     d0, d1 = run(case), run(case + "_ns")
