@@ -558,7 +558,7 @@ int mof_test_galerkin_launches(int64_t *counts);
  * meta[0..4) = zh in force, xm (level 0's corrected iterate: 1 bf16 in place,
  * 2 float2), the first level of the fused k_subcycle, row blocks per system.
  * Any output but z may be NULL. On a decomposed part's handle
- * (mof_dd_test_part) the cycle runs as pcg_dd calls it: zh = -1 means float2,
+ * (mof_dd_test_part) the cycle runs as pcg() calls it on the parts: zh = -1 means float2,
  * and rz sums the records of the owned rows alone. */
 int mof_test_amg_vcycle(mof_mesh *mesh, int32_t B, const float *r, const int32_t *smap, int32_t nl,
                         const uint8_t *retired, int32_t zh, int32_t tap, const uint32_t *sentinel, uint32_t *z,
@@ -770,8 +770,8 @@ int mof_dd_test_halo(mof_dd *dd, int32_t B, int32_t which, int32_t f32, const vo
  * back. */
 int mof_dd_test_gather(mof_dd *dd, int32_t B, const double *x64, const uint8_t *failed, const uint64_t *prefill,
                        double *V);
-/* Test hook: mof_test_pcg_inner for the decomposed driver (pcg_dd<V>() of
- * mof_pcg.hip: its own launches, halo exchanges, record all-gathers and
+/* Test hook: mof_test_pcg_inner for the decomposed solve (pcg<V>() of
+ * mof_pcg.hip over the parts: its own launches, halo exchanges, record all-gathers and
  * chunks) on a given right-hand side per local part, capped at max_iter
  * iterations; a capped solve fails no system. The in-process handle has just
  * solved exactly one batch of B systems with the preconditioner and precision

@@ -2691,7 +2691,7 @@ int mof_test_amg_vcycle(mof_mesh *m, int32_t B, const float *r, const int32_t *s
         for (int32_t l = 0; smap && l < nl; ++l) MOF_REQUIRE(smap[l] >= 0 && smap[l] < B, "bad system map");
         for (int32_t k = 0; k < nsys; ++k)
             MOF_REQUIRE(systems && systems[k] >= 0 && systems[k] < B, "bad system to read back");
-        // a decomposed part: the cycle as pcg_dd runs it (float2 z, the sums over the owned rows)
+        // a decomposed part: the cycle as pcg() runs it on the parts (float2 z, the sums over the owned rows)
         const bool zhb = zh < 0 ? (G.regular && m->n_own == m->N) : zh != 0;
         const int32_t L = (int32_t)G.lv.size();
         const size_t N = (size_t)m->N, nv = N * B;

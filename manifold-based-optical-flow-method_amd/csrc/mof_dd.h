@@ -4,7 +4,7 @@
 // lockstep with a halo exchange of the SpMV operand and cross-part reductions
 // of the CG scalars.
 //
-// Two transports behind one solver loop (mof_pcg.hip, solve_batch_dd):
+// Two transports behind one solver loop (mof_pcg.hip: refine() and pcg() over the local parts):
 //  * in-process: all P parts in one process on one device (one stream); the
 //    halo is one gather kernel over the ghost rows of every part and the
 //    per-part partial sums live in one shared array (no copies);

@@ -764,7 +764,7 @@ int spmv_slot(const PcgArgs<V> &a, bool first) {
     return (f32 ? 0 : 8) + (first ? 4 : 0) + (f32 && a.zh ? 2 : 0) + (f32 && a.mat.sell_idx ? 1 : 0);
 }
 template <typename V>
-void launch_spmv(const PcgArgs<V> &a, bool first, dim3, hipStream_t s, int32_t it, int32_t flags) {
+void launch_spmv(const PcgArgs<V> &a, bool first, hipStream_t s, int32_t it, int32_t flags) {
     ++g_pcg_launches[spmv_slot(a, first)];
     spmv_kernel(a, first)<<<spmv_grid(a), spmv_wg<V>(), 0, s>>>(a, it, flags);
 }
@@ -1459,8 +1459,10 @@ void launch_residual(mof_mesh *m, int32_t nblk, int32_t B, hipStream_t s, RedArg
     }
 }
 
+// amg: z and r.z come from m's V-cycle (fp32 only), with the level-0 smoother
+// data the init and the update write the pre-smoothing with
 template <typename V>
-PcgArgs<V> make_args(mof_mesh *m, int32_t B, const MatArgs<V> &mat, const V *dinv) {
+PcgArgs<V> make_args(mof_mesh *m, int32_t B, const MatArgs<V> &mat, const V *dinv, bool amg = false) {
     Workspace &w = m->ws;
     PcgArgs<V> a;
     a.N = m->N;
@@ -1489,8 +1491,100 @@ PcgArgs<V> make_args(mof_mesh *m, int32_t B, const MatArgs<V> &mat, const V *din
     a.stall = 0;
     a.sc = w.sc.p;
     a.zh = 0;
+    if constexpr (sizeof(V) == 4) {
+        if (amg) {
+            const AmgFine f = amg_fine(m);
+            a.ext = 1;
+            a.x0 = f.x0;
+            a.omega = f.omega;
+            a.dA = static_cast<const uint2 *>(f.A0h);
+            a.dA_nb = f.sell_nb;
+            a.dA_off = f.sell_off;
+        }
+    }
     return a;
 }
+
+// the workspace's assembled operator and block-Jacobi inverses of the working type
+template <typename V>
+const V *ws_A(const Workspace &w) {
+    if constexpr (sizeof(V) == 4)
+        return w.A32.p;
+    else
+        return w.A64.p;
+}
+template <typename V>
+const V *ws_dinv(const Workspace &w) {
+    if constexpr (sizeof(V) == 4)
+        return w.dinv32.p;
+    else
+        return w.dinv64.p;
+}
+
+// The local meshes of one solve, run in lockstep on one stream: the mesh of a
+// single-domain solve (d == nullptr), or the local parts of a decomposed one
+// (mof_dd.h): all P of an in-process handle, one of a rank's. Every stage of
+// pcg() and refine() is a loop over `mesh`, followed by halo() / sync() where
+// the parts refresh ghost rows or complete the shared partial records; both
+// do nothing on a single domain. Ghost rows are computed but never summed,
+// and every reduction runs over the [P][B][nmax] records of all parts in one
+// order, so all parts take the same decisions bit for bit.
+// "Single domain" is d == nullptr, never mesh.size() == 1: a rank with one
+// local part takes every host decision its peers take and enters every
+// collective.
+template <typename V>
+struct Parts {
+    mof_dd *d;
+    int32_t B;
+    std::vector<mof_mesh *> mesh;
+    mof_mesh *host;  // the mesh whose h_sysi / h_sysd mirror the host reads (all parts hold the same flags)
+    // the partial arrays and their record strides: the mesh's own (P = 1), or the handle's shared ones
+    double *part_pq, *part_rzrr, *part_rr0, *part_dx;
+    int32_t P, nmax, nvmax;
+    std::vector<RedArgs> rd, rdx;   // per mesh: the records of the row-block sums, of k_outer_update's maxima
+    std::vector<PcgArgs<V>> args;   // per mesh (fill_args)
+
+    Parts(mof_mesh *m, mof_dd *dd, int32_t nb) : d(dd), B(nb) {
+        if (d) {
+            mesh = d->parts;
+            part_pq = d->part_pq.p, part_rzrr = d->part_rzrr.p, part_rr0 = d->part_rr0.p, part_dx = d->part_dx.p;
+            P = d->P, nmax = d->nmax, nvmax = d->nvmax;
+            for (int32_t id : d->part_ids) {
+                rd.push_back(RedArgs{P, id, nmax, d->plan.parts[id].n_own});
+                rdx.push_back(RedArgs{P, id, nvmax, d->plan.parts[id].n_own});
+            }
+        } else {
+            Workspace &w = m->ws;
+            mesh = {m};
+            part_pq = w.part_pq.p, part_rzrr = w.part_rzrr.p, part_rr0 = w.part_rr0.p, part_dx = w.part_dx.p;
+            P = 1, nmax = w.nblk, nvmax = (m->N + kWG - 1) / kWG;
+            rd = {RedArgs{1, 0, nmax, m->N}};
+            rdx = {RedArgs{1, 0, nvmax, m->N}};
+        }
+        host = mesh[0];
+    }
+    // once the multigrid's storage and damping of this solve are in place (make_args reads them)
+    void fill_args(bool amg, int32_t stall) {
+        args.clear();
+        for (size_t l = 0; l < mesh.size(); ++l) {
+            const Workspace &w = mesh[l]->ws;
+            PcgArgs<V> a = make_args<V>(mesh[l], B, make_mat<V>(mesh[l], ws_A<V>(w)), ws_dinv<V>(w), amg);
+            a.part_pq = part_pq;
+            a.part_rzrr = part_rzrr;
+            a.red = rd[l];
+            a.stall = stall;
+            args.push_back(a);
+        }
+    }
+    // refresh the ghost rows of every part's z (which = 0) or x64 (which = 1)
+    void halo(int which, hipStream_t s) const {
+        if (d) dd_halo(d, B, which == 0 && sizeof(V) == 4, which, s);
+    }
+    // every part's records of one partial array, per_part doubles each, complete on every rank
+    void sync(double *base, size_t per_part, hipStream_t s) const {
+        if (d) dd_sync_partials(d, base, per_part, s);
+    }
+};
 
 void fetch_flags(mof_mesh *m, int32_t B, hipStream_t s) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -1521,22 +1615,23 @@ constexpr double kCompactFrac = 0.9;
 constexpr int32_t kBulkHint = 48;
 constexpr double kBulkFrac = 0.9;
 
+// Iterations of a system in an inner solve that has queued `it` of them:
+// SI_CONV (the SpMV launch that saw it converged), f + 1 after a failure at
+// update iteration f, all `it` if it is still running or failed at the cap.
+inline int32_t sys_iters(const int32_t *si, int32_t it) {
+    if (si[SI_CONV] >= 0) return si[SI_CONV];
+    return si[SI_FAILED] && si[SI_FAIL_WHY] != FW_MAXITER ? si[SI_FAIL_IT] + 1 : it;
+}
+
 // Systems of a chunk [it0, it0 + n) each timed SpMV launch processed: system
-// b works in launch it while it < last_b (SI_CONV = the launch that saw it
-// converged; a failure at update iteration f: f + 1), all n launches if it
-// is still running.
+// b works in launch it while it < sys_iters(b).
 void charge_chunk(const mof_mesh *m, int32_t B, const std::vector<int32_t> &running_at, int32_t it0,
                   int32_t n, uint32_t precision, int32_t solve_systems, const std::vector<float> &ms,
                   SpmvTiming *t) {
     std::vector<int32_t> active(n, 0);
     for (int32_t b = 0; b < B; ++b) {
         if (!running_at[b]) continue;
-        const int32_t *si = m->h_sysi + b * kSysStride;
-        int32_t last = it0 + n;
-        if (si[SI_CONV] >= 0)
-            last = si[SI_CONV];
-        else if (si[SI_FAILED] && si[SI_FAIL_WHY] != FW_MAXITER)
-            last = si[SI_FAIL_IT] + 1;
+        const int32_t last = sys_iters(m->h_sysi + b * kSysStride, it0 + n);
         for (int32_t c = 0; c < n && it0 + c < last; ++c) active[c]++;
     }
     for (int32_t c = 0; c < n; ++c) {
@@ -1551,46 +1646,91 @@ void charge_chunk(const mof_mesh *m, int32_t B, const std::vector<int32_t> &runn
     }
 }
 
-// Inner PCG on all active systems; returns iterations summed over systems.
+// Inner PCG on all active systems of every local part (rhs: one per part);
+// returns iterations summed over systems. One iteration is, over all parts:
+// halo(z), the SpMV, sync(p.q), k_red_pq, the update, k_pcg_conv_early, the
+// V-cycles, sync(r.z, |r|^2), k_red_rzrr.
 template <typename V>
-int64_t pcg(mof_mesh *m, int32_t B, const MatArgs<V> &mat, const V *dinv, const double *rhs,
-            double rtol, const SolveParams &sp, hipStream_t s, int32_t *max_iters, SpmvTiming *timing,
-            int32_t *hint, bool amg, double outer_rtol = 0.0, double etol = 0.0) {
-    const int32_t max_iter = sp.max_iter;
-    PcgArgs<V> a = make_args<V>(m, B, mat, dinv);
-    a.ext = amg ? 1 : 0;
-    a.stall = sp.stall;
-    if constexpr (sizeof(V) == 4) {
-        if (amg) {
-            AmgFine f = amg_fine(m);
-            a.x0 = f.x0;
-            a.omega = f.omega;
-            a.dA = static_cast<const uint2 *>(f.A0h);
-            a.dA_nb = f.sell_nb;
-            a.dA_off = f.sell_off;
-            // bf16 z on regular meshes with the tentative prolongator (C3
-            // +1 %, C2 mixed +2 %, same iterations); R3 on the smoothed one:
-            // 63 vs 50 its
-            a.zh = f.regular;
-        }
-    }
-    const int64_t ps = (int64_t)B * m->ws.nblk * 2;  // part_rzrr slot stride
+int64_t pcg(Parts<V> &p, const double *const *rhs, double rtol, const SolveParams &sp, hipStream_t s,
+            int32_t *max_iters, SpmvTiming *timing, int32_t *hint, bool amg, double outer_rtol = 0.0,
+            double etol = 0.0) {
+    const int32_t max_iter = sp.max_iter, B = p.B;
+    const size_t L = p.mesh.size();
+    mof_mesh *mh = p.host;
+    std::vector<PcgArgs<V>> &args = p.args;
+    // What saves launches, so far on a single domain only (there: one mesh, args[0]):
+    const bool single = p.d == nullptr;
+    // launches over the running systems alone (SysMap, kCompactFrac)
+    const bool compact = single;
+    // a mesh of at most kSelfRedBlk row blocks: the SpMV and the update
+    // reduce their scalars themselves (same bits as the k_red_* launches)
+    const bool selfred = single && args[0].red.P == 1 && args[0].nblk <= kSelfRedBlk;
     // a system converged after the update skips that iteration's V-cycle
     // (k_pcg_conv_early; same bits: its z was never used)
-    const bool early = amg;
-    // z = M^-1 r for the external preconditioner, r.z into slot `slot`
-    auto precond = [&](int32_t slot) {
+    const bool early = amg && single;
+    // bf16 z on regular meshes with the tentative prolongator (C3 +1 %, C2
+    // mixed +2 %, same iterations); R3 on the smoothed one: 63 vs 50 its.
+    // The halo exchange moves float2 z
+    bool zh = false;
+    if constexpr (sizeof(V) == 4) zh = amg && single && amg_fine(p.mesh[0]).regular;
+    // the first chunk stops where the bulk of the previous batch's systems had converged (hint[kBulkHint])
+    const bool bulk_hint = single;
+    // the SpMV launches carry events (charge_chunk)
+    const bool timed = timing && single;
+    // the per-system tolerance of a later refinement step (k_pcg_tol): the parts' stop rule ignores both
+    if (!single) outer_rtol = etol = 0.0;
+    for (PcgArgs<V> &a : args) {
+        a.sm = sys_all(B);
+        a.selfred = selfred;
+        a.zh = zh;
+    }
+    const int64_t rec = (int64_t)B * p.nmax;  // records of one part
+    const int64_t pqs = p.P * rec, ps = 2 * pqs;  // slot strides of part_pq, part_rzrr
+    // z = M^-1 r per part (block Jacobi over the parts, a V-cycle inside
+    // each), r.z into slot `slot`
+    auto cycles = [&](int32_t slot) {
         if constexpr (sizeof(V) == 4)
-            amg_vcycle(m, B, a.r, a.z, a.part_rzrr + slot * ps, a.nblk, a.red, s, a.zh != 0, a.sm.map, a.sm.n);
+            for (size_t l = 0; l < L; ++l)
+                amg_vcycle(p.mesh[l], B, args[l].r, args[l].z, p.part_rzrr + slot * ps, args[l].nblk, args[l].red, s,
+                           zh, args[l].sm.map, args[l].sm.n);
     };
-    dim3 g((unsigned)m->ws.nblk, (unsigned)B);
-    const dim3 gx(xcd_grid(m->ws.nblk, B, kGrpSpmv));
+    auto sync_rzrr = [&](int32_t slot) { p.sync(p.part_rzrr + slot * ps, 2 * rec, s); };
+    auto red_rzrr = [&](int32_t slot) {
+        if (selfred) return;
+        for (size_t l = 0; l < L; ++l) {
+            ++g_pcg_launches[kPcRedRzrr];
+            k_red_rzrr<V><<<dim3((unsigned)args[l].sm.n), kWG, 0, s>>>(args[l], slot);
+        }
+    };
+    auto red_pq = [&](int32_t slot) {
+        if (selfred) return;
+        for (size_t l = 0; l < L; ++l) {
+            ++g_pcg_launches[kPcRedPq];
+            k_red_pq<V><<<dim3((unsigned)args[l].sm.n), kWG, 0, s>>>(args[l], slot);
+        }
+    };
+    // SpMV launch `it_` of every part, its p.q records complete; e0, e1 (timed):
+    // events stamped by the kernel's own dispatch packet (start and end of its
+    // execution, as rocprof's kernel trace), not separate marker packets around it
+    auto spmv = [&](bool first, int32_t it_, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
+        p.halo(0, s);
+        for (size_t l = 0; l < L; ++l) {
+            const PcgArgs<V> &a = args[l];
+            if (e0) {
+                ++g_pcg_launches[spmv_slot(a, first)];
+                hipExtLaunchKernelGGL(spmv_kernel(a, first), spmv_grid(a), dim3(spmv_wg<V>()), 0, s, e0, e1, 0, a, it_, 0);
+            } else {
+                launch_spmv(a, first, s, it_, 0);
+            }
+        }
+        p.sync(p.part_pq + (it_ & 1) * pqs, rec, s);  // this parity's slot
+    };
     // systems active at the start of this solve: the host mirror is current
-    // (reset by solve_batch, refreshed by every outer check)
+    // (reset by refine, refreshed by every outer check)
     std::vector<int32_t> was_active(B), running_at(B);
     int32_t solve_systems = 0;
     for (int32_t b = 0; b < B; ++b) {
-        was_active[b] = m->h_sysi[b * kSysStride + SI_ACTIVE];
+        was_active[b] = mh->h_sysi[b * kSysStride + SI_ACTIVE];
         solve_systems += was_active[b];
     }
     running_at = was_active;
@@ -1598,26 +1738,29 @@ int64_t pcg(mof_mesh *m, int32_t B, const MatArgs<V> &mat, const V *dinv, const 
     // kCompactFrac of the batch (SysMap): a later refinement step's few
     // systems from the start, a long tail from its chunk boundary (same bits)
     std::vector<int32_t> h_map(B);  // read by the async upload until the next fetch_flags
-    if (solve_systems <= kCompactFrac * B) {
+    auto cover = [&](int32_t n) {   // h_map[0, n) (compact: one mesh)
+        int32_t *smap = p.mesh[0]->ws.smap.p;
+        MOF_HIP(hipMemcpyAsync(smap, h_map.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
+        args[0].sm = SysMap{smap, n};
+        ++g_pcg_launches[kPcCompact];
+    };
+    if (compact && solve_systems <= kCompactFrac * B) {
         int32_t n = 0;
         for (int32_t b = 0; b < B; ++b)
             if (was_active[b]) h_map[n++] = b;
-        if (n > 0) {
-            MOF_HIP(hipMemcpyAsync(m->ws.smap.p, h_map.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
-            a.sm = SysMap{m->ws.smap.p, n};
-            ++g_pcg_launches[kPcCompact];
-        }
+        if (n > 0) cover(n);
     }
-    // a mesh of at most kSelfRedBlk row blocks: the SpMV and the update
-    // reduce their scalars themselves (same bits as the k_red_* launches)
-    a.selfred = a.red.P == 1 && m->ws.nblk <= kSelfRedBlk ? 1 : 0;
-    k_pcg_init<V><<<g, kWG, 0, s>>>(a, rhs);
-    k_pcg_tol<V><<<dim3((unsigned)B), kWG, 0, s>>>(a, rtol, outer_rtol, etol);
-    if (amg) precond(0);
-    if (!a.selfred) {
-        ++g_pcg_launches[kPcRedRzrr];
-        k_red_rzrr<V><<<dim3((unsigned)a.sm.n), kWG, 0, s>>>(a, 0);
+    for (size_t l = 0; l < L; ++l)
+        k_pcg_init<V><<<dim3((unsigned)args[l].nblk, (unsigned)B), kWG, 0, s>>>(args[l], rhs[l]);
+    sync_rzrr(0);
+    // the tolerance step resets the convergence word the cycle's kernels
+    // check, so it runs before the first cycle
+    for (size_t l = 0; l < L; ++l) k_pcg_tol<V><<<dim3((unsigned)B), kWG, 0, s>>>(args[l], rtol, outer_rtol, etol);
+    if (amg) {
+        cycles(0);
+        sync_rzrr(0);
     }
+    red_rzrr(0);
     MOF_HIP(hipGetLastError());
     // The first chunk runs as many iterations as the same solve of the
     // previous batch needed (timesteps of one run converge alike), so the
@@ -1627,58 +1770,49 @@ int64_t pcg(mof_mesh *m, int32_t B, const MatArgs<V> &mat, const V *dinv, const 
     // the bulk of them, kBulkFrac) the first chunk stops at the bulk and the
     // rest runs compacted, straight to the previous slowest.
     int32_t it = 0;
-    const int32_t bulk = hint[kBulkHint];
+    const int32_t bulk = bulk_hint ? hint[kBulkHint] : 0;
     const bool split = bulk > 0 && *hint >= bulk + 2;
     int32_t chunk = split ? std::min(bulk, kMaxChunk) : (*hint > 0 ? std::min(*hint, kMaxChunk) : 8);
     bool done = false;
-    std::vector<hipEvent_t> &ev = m->spmv_events;
+    std::vector<hipEvent_t> &ev = mh->spmv_events;
     std::vector<float> ms;
     while (!done && it < max_iter) {
         const int32_t n = std::min(chunk, max_iter - it);
-        if (timing && (int32_t)ev.size() < 2 * n) {
+        if (timed && (int32_t)ev.size() < 2 * n) {
             const size_t old = ev.size();
             ev.resize(2 * (size_t)std::max(n, 64));
             for (size_t q = old; q < ev.size(); ++q) MOF_HIP(hipEventCreate(&ev[q]));
         }
         const int32_t it0 = it;
         for (int32_t c = 0; c < n; ++c, ++it) {
-            if (timing) {
-                // events stamped by the kernel's own dispatch packet (start
-                // and end of its execution, as rocprof's kernel trace), not
-                // separate marker packets around it
-                ++g_pcg_launches[spmv_slot(a, it == 0)];
-                hipExtLaunchKernelGGL(spmv_kernel(a, it == 0), spmv_grid(a), dim3(spmv_wg<V>()), 0, s, ev[2 * c], ev[2 * c + 1], 0, a, it, 0);
-            } else {
-                launch_spmv(a, it == 0, gx, s, it, 0);
+            if (timed)
+                spmv(it == 0, it, ev[2 * c], ev[2 * c + 1]);
+            else
+                spmv(it == 0, it);
+            red_pq(it & 1);
+            for (const PcgArgs<V> &a : args) {
+                ++g_pcg_launches[kPcUpdate];
+                k_pcg_update<V><<<dim3(upd_blocks(a.nblk), (unsigned)a.sm.n), kWG, 0, s>>>(a, it);
             }
-            const unsigned nl = (unsigned)a.sm.n;
-            if (!a.selfred) {
-                ++g_pcg_launches[kPcRedPq];
-                k_red_pq<V><<<dim3(nl), kWG, 0, s>>>(a, it & 1);
-            }
-            ++g_pcg_launches[kPcUpdate];
-            k_pcg_update<V><<<dim3(upd_blocks(m->ws.nblk), nl), kWG, 0, s>>>(a, it);
-            if (early) {
+            for (size_t l = 0; early && l < L; ++l) {
                 ++g_pcg_launches[kPcConvEarly];
-                k_pcg_conv_early<V><<<dim3(nl), kWG, 0, s>>>(a, it);
+                k_pcg_conv_early<V><<<dim3((unsigned)args[l].sm.n), kWG, 0, s>>>(args[l], it);
             }
-            if (amg) precond((it + 1) & 1);
-            if (!a.selfred) {
-                ++g_pcg_launches[kPcRedRzrr];
-                k_red_rzrr<V><<<dim3(nl), kWG, 0, s>>>(a, (it + 1) & 1);
-            }
+            if (amg) cycles((it + 1) & 1);
+            sync_rzrr((it + 1) & 1);
+            red_rzrr((it + 1) & 1);
         }
         MOF_HIP(hipGetLastError());
-        fetch_flags(m, B, s);
-        if (timing) {
+        fetch_flags(mh, B, s);
+        if (timed) {
             ms.assign(n, 0.f);
             for (int32_t c = 0; c < n; ++c) MOF_HIP(hipEventElapsedTime(&ms[c], ev[2 * c], ev[2 * c + 1]));
-            charge_chunk(m, B, running_at, it0, n, sp.precision, solve_systems, ms, timing);
+            charge_chunk(mh, B, running_at, it0, n, sp.precision, solve_systems, ms, timing);
         }
         done = true;
         int32_t owe_or_run = 0;
         for (int32_t b = 0; b < B; ++b) {
-            const int32_t *si = m->h_sysi + b * kSysStride;
+            const int32_t *si = mh->h_sysi + b * kSysStride;
             running_at[b] = si[SI_ACTIVE] && !si[SI_FAILED] && si[SI_CONV] < 0;
             if (running_at[b]) done = false;
             // the next chunk's launches: the running systems and those owed
@@ -1689,28 +1823,27 @@ int64_t pcg(mof_mesh *m, int32_t B, const MatArgs<V> &mat, const V *dinv, const 
         chunk = split && it == std::min(bulk, kMaxChunk) && *hint > it ? std::min(*hint - it, kMaxChunk) : 8;
         // a tail chunk (at most kCompactFrac of the batch still running)
         // launches over those systems only; same bits (SysMap)
-        if (!done && owe_or_run <= kCompactFrac * B) {
-            MOF_HIP(hipMemcpyAsync(m->ws.smap.p, h_map.data(), sizeof(int32_t) * owe_or_run, hipMemcpyHostToDevice, s));
-            a.sm = SysMap{m->ws.smap.p, owe_or_run};
-            ++g_pcg_launches[kPcCompact];
-        }
+        if (compact && !done && owe_or_run <= kCompactFrac * B) cover(owe_or_run);
     }
     if (!done) {
         // one more check launch so SI_CONV records systems converged at max_iter
         // (it == 0 only with max_iter = 0, the test hook's cap 0: the first instance, which reads
-        // no previous iteration's scalars)
-        launch_spmv(a, it == 0, gx, s, it, 0);
-        if (sp.fail_at_max_iter) k_fail_running<<<dim3((unsigned)((B + 63) / 64)), 64, 0, s>>>(B, it, a.sysi);
+        // no previous iteration's scalars); on parts its p.q is reduced like any SpMV's (no launch reads it)
+        spmv(it == 0, it);
+        if (!single) red_pq(it & 1);
+        if (sp.fail_at_max_iter)
+            for (const PcgArgs<V> &a : args)
+                k_fail_running<<<dim3((unsigned)((B + 63) / 64)), 64, 0, s>>>(B, it, a.sysi);
         MOF_HIP(hipGetLastError());
-        fetch_flags(m, B, s);
+        fetch_flags(mh, B, s);
     } else if (early) {
         // systems marked by the last queued iteration (SI_CONV == it) still
         // owe the deferred x += alpha p of SpMV launch `it`: that launch alone
         // (every other system is retired in it)
         bool owe = false;
         for (int32_t b = 0; b < B && !owe; ++b)
-            owe = was_active[b] && m->h_sysi[b * kSysStride + SI_CONV] == it;
-        if (owe) launch_spmv(a, false, gx, s, it, 0);
+            owe = was_active[b] && mh->h_sysi[b * kSysStride + SI_CONV] == it;
+        if (owe) spmv(false, it);
         MOF_HIP(hipGetLastError());
     }
     int64_t total = 0;
@@ -1718,14 +1851,13 @@ int64_t pcg(mof_mesh *m, int32_t B, const MatArgs<V> &mat, const V *dinv, const 
     std::vector<int32_t> convs;
     for (int32_t b = 0; b < B; ++b) {
         if (!was_active[b]) continue;
-        const int32_t *si = m->h_sysi + b * kSysStride;
-        const int32_t c = si[SI_CONV];
-        const int32_t its = c >= 0 ? c : (si[SI_FAILED] && si[SI_FAIL_WHY] != FW_MAXITER ? si[SI_FAIL_IT] + 1 : it);
+        const int32_t *si = mh->h_sysi + b * kSysStride;
+        const int32_t c = si[SI_CONV], its = sys_iters(si, it);
         total += its;
         slowest = std::max(slowest, its);
         if (c >= 0) {
             slowest_conv = std::max(slowest_conv, c);
-            convs.push_back(c);
+            if (bulk_hint) convs.push_back(c);
         }
     }
     if (!convs.empty()) {
@@ -1741,6 +1873,137 @@ int64_t pcg(mof_mesh *m, int32_t B, const MatArgs<V> &mat, const V *dinv, const 
     // at the flags)
     if (slowest_conv > 0) *hint = std::min(slowest_conv + (early ? 0 : 1), kMaxChunk);
     return total;
+}
+
+// the recovery's damped pass: the meshes' smoother damping for this solve only
+struct OmegaScope {
+    const std::vector<mof_mesh *> &mesh;
+    std::vector<float> old;
+    OmegaScope(const std::vector<mof_mesh *> &ms, float om, bool use) : mesh(ms) {
+        if (use && om > 0.f)
+            for (mof_mesh *m : mesh) old.push_back(amg_set_omega(m, om));
+    }
+    ~OmegaScope() {
+        for (size_t l = 0; l < old.size(); ++l) amg_set_omega(mesh[l], old[l]);
+    }
+};
+
+// The eager solve of a batch on one mesh (d null) or on d's local parts:
+// inner PCG in the working type V, fp64 iterative refinement around it.
+template <typename V>
+int64_t refine(mof_mesh *m, mof_dd *d, int32_t B, const SolveParams &sp, hipStream_t s, int32_t *outer,
+               int32_t *max_iters, SpmvTiming *tm, const uint8_t *only) {
+    constexpr bool f32 = sizeof(V) == 4;
+    Parts<V> p(m, d, B);
+    const size_t L = p.mesh.size();
+    mof_mesh *mh = p.host;
+    const dim3 gsys((unsigned)((B + 63) / 64));
+    // a fresh solve resets every system; with `only`, the selected systems
+    // are re-solved from x = 0 and the others stay retired with their
+    // solution, residual and flags (the host mirror is the state of the
+    // previous solve's last fetch; every part holds the same flags)
+    if (!only) {
+        for (mof_mesh *q : p.mesh) k_sys_reset<<<gsys, 64, 0, s>>>(B, q->ws.sysi.p, q->ws.sysd.p);
+        MOF_HIP(hipGetLastError());
+    }
+    for (int32_t b = 0; b < B; ++b) {
+        if (only && !only[b]) continue;
+        int32_t *si = mh->h_sysi + b * kSysStride;
+        for (int k = 0; k < kSysStride; ++k) si[k] = 0;
+        si[SI_ACTIVE] = 1;
+        si[SI_CONV] = -1;
+    }
+    if (only)
+        for (mof_mesh *q : p.mesh)
+            MOF_HIP(hipMemcpyAsync(q->ws.sysi.p, mh->h_sysi, sizeof(int32_t) * kSysStride * B, hipMemcpyHostToDevice,
+                                   s));
+    if (d) {
+        // records of workgroups past a part's own count must read as zero, and
+        // their positions move with B: clear the shared arrays per batch
+        MOF_HIP(hipMemsetAsync(d->part_pq.p, 0, d->part_pq.bytes(), s));
+        MOF_HIP(hipMemsetAsync(d->part_rzrr.p, 0, d->part_rzrr.bytes(), s));
+        MOF_HIP(hipMemsetAsync(d->part_rr0.p, 0, d->part_rr0.bytes(), s));
+        MOF_HIP(hipMemsetAsync(d->part_dx.p, 0, d->part_dx.bytes(), s));
+    }
+    // the multigrid on every part, or on none
+    bool amg = sp.amg && f32;
+    for (size_t l = 0; l < L && amg; ++l) amg = amg_build(p.mesh[l]);
+    if (amg)
+        for (mof_mesh *q : p.mesh) {
+            amg_ensure(q, B);
+            // a recovery pass (only) re-solves systems of this batch, whose
+            // coarse operators are still in place
+            if (!only) amg_setup_batch(q, B, s);
+        }
+    OmegaScope omega_scope(p.mesh, sp.amg_omega, amg);
+    p.fill_args(amg, sp.stall);
+    // pcg's hints per (precision, preconditioner, refinement step), on a
+    // single domain followed by its bulk hints
+    std::vector<int32_t> &hints = mh->iter_hint;
+    const size_t nhint = d ? 2 * 16 : 2 * kBulkHint;
+    if (hints.size() < nhint) hints.assign(nhint, 0);
+    const int32_t hint0 = !f32 ? 0 : (d || amg ? 16 : 32);
+    std::vector<const double *> rhs(L);
+    int64_t iters = 0, iters_before = 0;
+    int32_t o = 0;
+    // MOF_VERBOSE: per refinement step iterations and residuals on stderr
+    static const bool verbose = knob(Knob::Verbose) != nullptr;
+    for (; o < sp.max_outer; ++o) {
+        for (size_t l = 0; l < L; ++l) rhs[l] = o == 0 ? p.mesh[l]->ws.rhs.p : p.mesh[l]->ws.r64.p;
+        // the fp64 solve's first step to 0.5 rtol
+        iters += pcg<V>(p, rhs.data(), !f32 && o == 0 ? 0.5 * sp.rtol : sp.inner_rtol, sp, s, max_iters, tm,
+                        &hints[hint0 + std::min(o, 15)], amg, o > 0 && sp.adaptive_inner ? sp.rtol : 0.0, sp.etol);
+        for (size_t l = 0; l < L; ++l) {
+            mof_mesh *q = p.mesh[l];
+            Workspace &w = q->ws;
+            const dim3 gv((unsigned)((q->N + kWG - 1) / kWG), (unsigned)B);  // one row per thread
+            ++g_pcg_launches[kPcOuterUpdate];
+            k_outer_update<V><<<gv, kWG, 0, s>>>(q->N, o == 0, p.args[l].x, w.sysi.p, w.x64.p, p.rdx[l], B, p.part_dx);
+        }
+        p.sync(p.part_dx, 2 * (size_t)B * p.nvmax, s);
+        p.halo(1, s);  // the residual reads x64 at the ghosts
+        for (size_t l = 0; l < L; ++l) {
+            Workspace &w = p.mesh[l]->ws;
+            launch_residual(p.mesh[l], w.nblk, B, s, p.rd[l], w.rhs.p, w.x64.p, w.sysi.p, w.r64.p, p.part_rr0);
+        }
+        p.sync(p.part_rr0, 2 * (size_t)B * p.nmax, s);
+        for (size_t l = 0; l < L; ++l) {
+            Workspace &w = p.mesh[l]->ws;
+            RedArgs rd = p.rd[l], rdx = p.rdx[l];
+            if (d) rd.nown = rdx.nown = 0;  // the check sums records, not rows: the parts pass no row count
+            ++g_pcg_launches[kPcOuterCheck];
+            k_outer_check<<<dim3((unsigned)B), kWG, 0, s>>>(rd, B, p.part_rr0, rdx, p.part_dx, o == 0, sp.rtol,
+                                                            sp.etol, w.sysd.p, w.sysi.p);
+        }
+        MOF_HIP(hipGetLastError());
+        fetch_flags(mh, B, s);
+        bool any = false;
+        for (int32_t b = 0; b < B; ++b) any |= mh->h_sysi[b * kSysStride + SI_ACTIVE] != 0;
+        if (verbose) {
+            double worst = 0.0, west = 0.0;
+            int32_t act = 0;
+            for (int32_t b = 0; b < B; ++b) {
+                const double *sd = mh->h_sysd + b * kSysStride;
+                worst = std::max(worst, sd[SD_REL]);
+                if (sd[SD_XMAX] > 0.0) west = std::max(west, sd[SD_EST] / sd[SD_XMAX]);
+                act += mh->h_sysi[b * kSysStride + SI_ACTIVE] != 0;
+            }
+            std::fprintf(stderr,
+                         "[mof solve] B=%d outer %d: %lld inner its (sum), max rel residual %.3e, max error est %.3e "
+                         "of max|V|, %d still active\n",
+                         B, o, (long long)(iters - iters_before), worst, west, act);
+            iters_before = iters;
+        }
+        if (!any) {
+            ++o;
+            break;
+        }
+    }
+    for (mof_mesh *q : p.mesh) k_mark_unconverged<<<gsys, 64, 0, s>>>(B, sp.rtol, q->ws.sysd.p, q->ws.sysi.p);
+    MOF_HIP(hipGetLastError());
+    fetch_flags(mh, B, s);
+    *outer = o;
+    return iters;
 }
 
 // ---- the fused small-mesh solve ---------------------------------------------
@@ -1988,7 +2251,7 @@ int64_t solve_batch(mof_mesh *m, int32_t B, const SolveParams &sp, hipStream_t s
     Workspace &w = m->ws;
     if (fused_eligible(m, sp, only)) {
         // the whole solve in one launch (k_solve_fused), bit-identical to the
-        // eager loop below
+        // eager loop (refine)
         PcgArgs<double> a = make_args<double>(m, B, make_mat<double>(m, w.A64.p), w.dinv64.p);
         a.stall = sp.stall;
         const FusedArgs fa{w.rhs.p, w.x64.p,   w.r64.p,     w.part_rr0.p, w.part_dx.p,
@@ -2030,345 +2293,15 @@ int64_t solve_batch(mof_mesh *m, int32_t B, const SolveParams &sp, hipStream_t s
         }
         return iters;
     }
-    if (!only) {
-        k_sys_reset<<<dim3((unsigned)((B + 63) / 64)), 64, 0, s>>>(B, w.sysi.p, w.sysd.p);
-        MOF_HIP(hipGetLastError());
-        for (int32_t b = 0; b < B; ++b) {  // host mirror of the reset state
-            int32_t *si = m->h_sysi + b * kSysStride;
-            for (int k = 0; k < kSysStride; ++k) si[k] = 0;
-            si[SI_ACTIVE] = 1;
-            si[SI_CONV] = -1;
-        }
-    } else {
-        // re-solve the selected systems from x = 0; the others stay retired
-        // with their solution, residual and flags (the host mirror is the
-        // state of the previous solve's last fetch)
-        for (int32_t b = 0; b < B; ++b) {
-            int32_t *si = m->h_sysi + b * kSysStride;
-            if (!only[b]) continue;
-            for (int k = 0; k < kSysStride; ++k) si[k] = 0;
-            si[SI_ACTIVE] = 1;
-            si[SI_CONV] = -1;
-        }
-        MOF_HIP(hipMemcpyAsync(w.sysi.p, m->h_sysi, sizeof(int32_t) * kSysStride * B, hipMemcpyHostToDevice, s));
-    }
-    if (m->iter_hint.size() < 2 * kBulkHint) m->iter_hint.assign(2 * kBulkHint, 0);  // + pcg's bulk hints
-    const bool amg = sp.amg && sp.precision == MOF_PREC_MIXED && amg_build(m);
-    if (amg) {
-        amg_ensure(m, B);
-        // a recovery pass (only) re-solves systems of this batch, whose
-        // coarse operators are still in place
-        if (!only) amg_setup_batch(m, B, s);
-    }
-    // the recovery's damped pass: its smoother damping for this solve only
-    struct OmegaScope {
-        mof_mesh *m;
-        float old = 0.f;
-        bool on;
-        OmegaScope(mof_mesh *mm, float om, bool use) : m(mm), on(use && om > 0.f) {
-            if (on) old = amg_set_omega(m, om);
-        }
-        ~OmegaScope() {
-            if (on) amg_set_omega(m, old);
-        }
-    } omega_scope(m, sp.amg_omega, amg);
-    dim3 g((unsigned)w.nblk, (unsigned)B);
-    dim3 gv((unsigned)((m->N + kWG - 1) / kWG), (unsigned)B);  // one row per thread
-    const RedArgs rdx{1, 0, (int32_t)gv.x, m->N};                 // k_outer_update's max records
-    int64_t iters = 0, iters_before = 0;
-    int32_t o = 0;
-    // MOF_VERBOSE: per refinement step iterations and residuals on stderr
-    static const bool verbose = knob(Knob::Verbose) != nullptr;
-    for (; o < sp.max_outer; ++o) {
-        const double *rhs = (o == 0) ? w.rhs.p : w.r64.p;
-        if (sp.precision == MOF_PREC_MIXED) {
-            // hints per (precision, preconditioner, refinement step)
-            iters += pcg<float>(m, B, make_mat<float>(m, w.A32.p), w.dinv32.p, rhs, sp.inner_rtol, sp, s,
-                                max_iters, tm, &m->iter_hint[(amg ? 16 : 32) + std::min(o, 15)], amg,
-                                o > 0 && sp.adaptive_inner ? sp.rtol : 0.0, sp.etol);
-            ++g_pcg_launches[kPcOuterUpdate];
-            k_outer_update<float><<<gv, kWG, 0, s>>>(m->N, o == 0, reinterpret_cast<float *>(w.vx.p),
-                                                    w.sysi.p, w.x64.p, rdx, B, w.part_dx.p);
-        } else {
-            iters += pcg<double>(m, B, make_mat<double>(m, w.A64.p), w.dinv64.p, rhs,
-                                 o == 0 ? 0.5 * sp.rtol : sp.inner_rtol, sp, s, max_iters, tm,
-                                 &m->iter_hint[std::min(o, 15)], false, o > 0 && sp.adaptive_inner ? sp.rtol : 0.0,
-                                 sp.etol);
-            ++g_pcg_launches[kPcOuterUpdate];
-            k_outer_update<double><<<gv, kWG, 0, s>>>(m->N, o == 0, w.vx.p, w.sysi.p, w.x64.p, rdx, B,
-                                                     w.part_dx.p);
-        }
-        const RedArgs rd{1, 0, w.nblk, m->N};
-        launch_residual(m, w.nblk, B, s, rd, w.rhs.p, w.x64.p, w.sysi.p,
-                                                              w.r64.p, w.part_rr0.p);
-        ++g_pcg_launches[kPcOuterCheck];
-        k_outer_check<<<dim3((unsigned)B), kWG, 0, s>>>(rd, B, w.part_rr0.p, rdx, w.part_dx.p, o == 0, sp.rtol,
-                                                        sp.etol, w.sysd.p, w.sysi.p);
-        MOF_HIP(hipGetLastError());
-        fetch_flags(m, B, s);
-        bool any = false;
-        for (int32_t b = 0; b < B; ++b) any |= m->h_sysi[b * kSysStride + SI_ACTIVE] != 0;
-        if (verbose) {
-            double worst = 0.0, west = 0.0;
-            int32_t act = 0;
-            for (int32_t b = 0; b < B; ++b) {
-                const double *sd = m->h_sysd + b * kSysStride;
-                worst = std::max(worst, sd[SD_REL]);
-                if (sd[SD_XMAX] > 0.0) west = std::max(west, sd[SD_EST] / sd[SD_XMAX]);
-                act += m->h_sysi[b * kSysStride + SI_ACTIVE] != 0;
-            }
-            std::fprintf(stderr,
-                         "[mof solve] B=%d outer %d: %lld inner its (sum), max rel residual %.3e, max error est %.3e "
-                         "of max|V|, %d still active\n",
-                         B, o, (long long)(iters - iters_before), worst, west, act);
-            iters_before = iters;
-        }
-        if (!any) {
-            ++o;
-            break;
-        }
-    }
-    k_mark_unconverged<<<dim3((unsigned)((B + 63) / 64)), 64, 0, s>>>(B, sp.rtol, w.sysd.p, w.sysi.p);
-    MOF_HIP(hipGetLastError());
-    fetch_flags(m, B, s);
-    *outer = o;
-    return iters;
+    return sp.precision == MOF_PREC_MIXED ? refine<float>(m, nullptr, B, sp, s, outer, max_iters, tm, only)
+                                          : refine<double>(m, nullptr, B, sp, s, outer, max_iters, tm, only);
 }
 
-// ---- domain-decomposed solve (mof_dd.h): the same kernels on every local
-// part, in lockstep on one stream; ghost rows are computed but never summed,
-// the SpMV operand's ghosts are refreshed by the halo exchange, and every
-// reduction runs over the [P][B][nmax] records of all parts.
-namespace {
-
-template <typename V>
-std::vector<PcgArgs<V>> dd_args(mof_dd *d, int32_t B, bool amg) {
-    std::vector<PcgArgs<V>> args;
-    for (size_t l = 0; l < d->parts.size(); ++l) {
-        mof_mesh *m = d->parts[l];
-        Workspace &w = m->ws;
-        PcgArgs<V> a;
-        if constexpr (sizeof(V) == 4)
-            a = make_args<float>(m, B, make_mat<float>(m, w.A32.p), w.dinv32.p);
-        else
-            a = make_args<double>(m, B, make_mat<double>(m, w.A64.p), w.dinv64.p);
-        a.part_pq = d->part_pq.p;
-        a.part_rzrr = d->part_rzrr.p;
-        a.red = RedArgs{d->P, d->part_ids[l], d->nmax, d->plan.parts[d->part_ids[l]].n_own};
-        if constexpr (sizeof(V) == 4) {
-            if (amg) {  // subdomain multigrid: each part's cycle on its owned rows
-                const AmgFine f = amg_fine(m);
-                a.ext = 1;
-                a.x0 = f.x0;
-                a.omega = f.omega;
-                    a.dA = static_cast<const uint2 *>(f.A0h);
-                a.dA_nb = f.sell_nb;
-                a.dA_off = f.sell_off;
-            }
-        }
-        args.push_back(a);
-    }
-    return args;
-}
-
-template <typename V>
-int64_t pcg_dd(mof_dd *d, int32_t B, bool first_outer, double rtol, const SolveParams &sp, hipStream_t s,
-               int32_t *max_iters, int32_t *hint, bool amg) {
-    const int32_t max_iter = sp.max_iter;
-    std::vector<PcgArgs<V>> args = dd_args<V>(d, B, amg);
-    // the single-domain solve's failure tests: stagnation window, a capped
-    // multigrid solve fails the system (every part takes the same decision)
-    for (PcgArgs<V> &a : args) a.stall = sp.stall;
-    const size_t L = args.size();
-    mof_mesh *m0 = d->parts[0];
-    const int64_t rec = (int64_t)B * d->nmax;  // records of one part
-    const int64_t ps = (int64_t)d->P * rec * 2;
-    // z = M^-1 r per part (block Jacobi over the parts, a V-cycle inside
-    // each), r.z into slot `slot`; then the slot's records are complete
-    auto precond = [&](int32_t slot) {
-        if constexpr (sizeof(V) == 4) {
-            if (amg)
-                for (size_t l = 0; l < L; ++l)
-                    amg_vcycle(d->parts[l], B, args[l].r, args[l].z, d->part_rzrr.p + slot * ps,
-                               d->parts[l]->ws.nblk, args[l].red, s, false);
-        }
-        dd_sync_partials(d, d->part_rzrr.p + slot * ps, 2 * rec, s);
-        for (size_t l = 0; l < L; ++l) k_red_rzrr<V><<<dim3((unsigned)B), kWG, 0, s>>>(args[l], slot);
-    };
-    for (size_t l = 0; l < L; ++l) {
-        Workspace &w = d->parts[l]->ws;
-        const double *rhs = first_outer ? w.rhs.p : w.r64.p;
-        k_pcg_init<V><<<dim3((unsigned)w.nblk, (unsigned)B), kWG, 0, s>>>(args[l], rhs);
-    }
-    dd_sync_partials(d, d->part_rzrr.p, 2 * rec, s);
-    // the tolerance step resets the convergence word the cycle's kernels
-    // check, so it runs before the first cycle
-    for (size_t l = 0; l < L; ++l) k_pcg_tol<V><<<dim3((unsigned)B), kWG, 0, s>>>(args[l], rtol, 0.0, 0.0);
-    if (amg)
-        precond(0);
-    else
-        for (size_t l = 0; l < L; ++l) k_red_rzrr<V><<<dim3((unsigned)B), kWG, 0, s>>>(args[l], 0);
-    MOF_HIP(hipGetLastError());
-    std::vector<int32_t> was_active(B);
-    for (int32_t b = 0; b < B; ++b) was_active[b] = m0->h_sysi[b * kSysStride + SI_ACTIVE];
-    int32_t it = 0;
-    int32_t chunk = *hint > 0 ? std::min(*hint, kMaxChunk) : 8;
-    bool done = false;
-    auto spmv = [&](bool first, int32_t it_) {
-        dd_halo(d, B, sizeof(V) == 4, 0, s);
-        for (size_t l = 0; l < L; ++l) {
-            const dim3 gx(xcd_grid(d->parts[l]->ws.nblk, B, kGrpSpmv));
-            launch_spmv(args[l], first, gx, s, it_, 0);
-        }
-        dd_sync_partials(d, d->part_pq.p + (it_ & 1) * (int64_t)d->P * rec, rec, s);  // this parity's slot
-        for (size_t l = 0; l < L; ++l) k_red_pq<V><<<dim3((unsigned)B), kWG, 0, s>>>(args[l], it_ & 1);
-    };
-    while (!done && it < max_iter) {
-        const int32_t n = std::min(chunk, max_iter - it);
-        for (int32_t c = 0; c < n; ++c, ++it) {
-            spmv(it == 0, it);
-            for (size_t l = 0; l < L; ++l)
-                k_pcg_update<V><<<dim3(upd_blocks(d->parts[l]->ws.nblk), (unsigned)B), kWG, 0, s>>>(args[l], it);
-            precond((it + 1) & 1);
-        }
-        MOF_HIP(hipGetLastError());
-        fetch_flags(m0, B, s);
-        done = true;
-        for (int32_t b = 0; b < B; ++b) {
-            const int32_t *si = m0->h_sysi + b * kSysStride;
-            if (si[SI_ACTIVE] && !si[SI_FAILED] && si[SI_CONV] < 0) done = false;
-        }
-        chunk = 8;
-    }
-    if (!done) {
-        // (it == 0 only with max_iter = 0, the test hook's cap 0: the first instance, as in pcg())
-        spmv(it == 0, it);
-        if (sp.fail_at_max_iter)
-            for (size_t l = 0; l < L; ++l)
-                k_fail_running<<<dim3((unsigned)((B + 63) / 64)), 64, 0, s>>>(B, it, args[l].sysi);
-        MOF_HIP(hipGetLastError());
-        fetch_flags(m0, B, s);
-    }
-    int64_t total = 0;
-    int32_t slowest = 0, slowest_conv = 0;
-    for (int32_t b = 0; b < B; ++b) {
-        if (!was_active[b]) continue;
-        const int32_t *si = m0->h_sysi + b * kSysStride;
-        const int32_t c = si[SI_CONV];
-        const int32_t its = c >= 0 ? c : (si[SI_FAILED] && si[SI_FAIL_WHY] != FW_MAXITER ? si[SI_FAIL_IT] + 1 : it);
-        total += its;
-        slowest = std::max(slowest, its);
-        if (c >= 0) slowest_conv = std::max(slowest_conv, c);
-    }
-    *max_iters = std::max(*max_iters, slowest);
-    if (slowest_conv > 0) *hint = std::min(slowest_conv + 1, kMaxChunk);
-    return total;
-}
-
-}  // namespace
-
+// The domain-decomposed solve (mof_dd.h): the same loop over d's local parts.
 int64_t solve_batch_dd(mof_dd *d, int32_t B, const SolveParams &sp, hipStream_t s, int32_t *outer,
                        int32_t *max_iters, const uint8_t *only) {
-    const size_t L = d->parts.size();
-    mof_mesh *m0 = d->parts[0];
-    // records of workgroups past a part's own count must read as zero, and
-    // their positions move with B: clear the partial arrays per batch
-    MOF_HIP(hipMemsetAsync(d->part_pq.p, 0, d->part_pq.bytes(), s));
-    MOF_HIP(hipMemsetAsync(d->part_rzrr.p, 0, d->part_rzrr.bytes(), s));
-    MOF_HIP(hipMemsetAsync(d->part_rr0.p, 0, d->part_rr0.bytes(), s));
-    MOF_HIP(hipMemsetAsync(d->part_dx.p, 0, d->part_dx.bytes(), s));  // a smaller part's tail records stay 0
-    if (!only) {
-        for (size_t l = 0; l < L; ++l) {
-            Workspace &w = d->parts[l]->ws;
-            k_sys_reset<<<dim3((unsigned)((B + 63) / 64)), 64, 0, s>>>(B, w.sysi.p, w.sysd.p);
-        }
-        MOF_HIP(hipGetLastError());
-    }
-    for (int32_t b = 0; b < B; ++b) {
-        if (only && !only[b]) continue;
-        int32_t *si = m0->h_sysi + b * kSysStride;
-        for (int k = 0; k < kSysStride; ++k) si[k] = 0;
-        si[SI_ACTIVE] = 1;
-        si[SI_CONV] = -1;
-    }
-    if (only)  // every part holds the same flags (all take the same decisions)
-        for (size_t l = 0; l < L; ++l)
-            MOF_HIP(hipMemcpyAsync(d->parts[l]->ws.sysi.p, m0->h_sysi, sizeof(int32_t) * kSysStride * B,
-                                   hipMemcpyHostToDevice, s));
-    if (m0->iter_hint.size() < 2 * 16) m0->iter_hint.assign(2 * 16, 0);
-    bool amg = sp.amg && sp.precision == MOF_PREC_MIXED;
-    for (size_t l = 0; l < L && amg; ++l) amg = amg_build(d->parts[l]);
-    if (amg)
-        for (size_t l = 0; l < L; ++l) {
-            amg_ensure(d->parts[l], B);
-            if (!only) amg_setup_batch(d->parts[l], B, s);  // a recovery pass: still in place
-        }
-    // the recovery's damped pass: every part's smoother damping for this solve
-    std::vector<float> om_old(L, 0.f);
-    const bool om_set = amg && sp.amg_omega > 0.f;
-    if (om_set)
-        for (size_t l = 0; l < L; ++l) om_old[l] = amg_set_omega(d->parts[l], sp.amg_omega);
-    struct Restore {
-        std::function<void()> f;
-        ~Restore() { f(); }
-    } restore{[&] {
-        if (om_set)
-            for (size_t l = 0; l < L; ++l) amg_set_omega(d->parts[l], om_old[l]);
-    }};
-    int64_t iters = 0;
-    int32_t o = 0;
-    for (; o < sp.max_outer; ++o) {
-        if (sp.precision == MOF_PREC_MIXED)
-            iters += pcg_dd<float>(d, B, o == 0, sp.inner_rtol, sp, s, max_iters,
-                                   &m0->iter_hint[16 + std::min(o, 15)], amg);
-        else
-            iters += pcg_dd<double>(d, B, o == 0, o == 0 ? 0.5 * sp.rtol : sp.inner_rtol, sp, s,
-                                    max_iters, &m0->iter_hint[std::min(o, 15)], false);
-        for (size_t l = 0; l < L; ++l) {
-            mof_mesh *m = d->parts[l];
-            Workspace &w = m->ws;
-            dim3 gv((unsigned)((m->N + kWG - 1) / kWG), (unsigned)B);
-            const RedArgs rdx{d->P, d->part_ids[l], d->nvmax, d->plan.parts[d->part_ids[l]].n_own};
-            if (sp.precision == MOF_PREC_MIXED)
-                k_outer_update<float><<<gv, kWG, 0, s>>>(m->N, o == 0, reinterpret_cast<float *>(w.vx.p),
-                                                        w.sysi.p, w.x64.p, rdx, B, d->part_dx.p);
-            else
-                k_outer_update<double><<<gv, kWG, 0, s>>>(m->N, o == 0, w.vx.p, w.sysi.p, w.x64.p, rdx, B,
-                                                         d->part_dx.p);
-        }
-        dd_sync_partials(d, d->part_dx.p, 2 * (int64_t)B * d->nvmax, s);
-        dd_halo(d, B, false, 1, s);  // the residual reads x64 at the ghosts
-        for (size_t l = 0; l < L; ++l) {
-            mof_mesh *m = d->parts[l];
-            Workspace &w = m->ws;
-            const RedArgs rd{d->P, d->part_ids[l], d->nmax, d->plan.parts[d->part_ids[l]].n_own};
-            launch_residual(m, w.nblk, B, s, rd, w.rhs.p, w.x64.p,
-                                                                  w.sysi.p, w.r64.p, d->part_rr0.p);
-        }
-        dd_sync_partials(d, d->part_rr0.p, 2 * (int64_t)B * d->nmax, s);
-        for (size_t l = 0; l < L; ++l) {
-            Workspace &w = d->parts[l]->ws;
-            const RedArgs rd{d->P, d->part_ids[l], d->nmax, 0};
-            const RedArgs rdx{d->P, d->part_ids[l], d->nvmax, 0};
-            k_outer_check<<<dim3((unsigned)B), kWG, 0, s>>>(rd, B, d->part_rr0.p, rdx, d->part_dx.p, o == 0, sp.rtol,
-                                                            sp.etol, w.sysd.p, w.sysi.p);
-        }
-        MOF_HIP(hipGetLastError());
-        fetch_flags(m0, B, s);
-        bool any = false;
-        for (int32_t b = 0; b < B; ++b) any |= m0->h_sysi[b * kSysStride + SI_ACTIVE] != 0;
-        if (!any) {
-            ++o;
-            break;
-        }
-    }
-    for (size_t l = 0; l < L; ++l)
-        k_mark_unconverged<<<dim3((unsigned)((B + 63) / 64)), 64, 0, s>>>(B, sp.rtol, d->parts[l]->ws.sysd.p,
-                                                                          d->parts[l]->ws.sysi.p);
-    MOF_HIP(hipGetLastError());
-    fetch_flags(m0, B, s);
-    *outer = o;
-    return iters;
+    return sp.precision == MOF_PREC_MIXED ? refine<float>(nullptr, d, B, sp, s, outer, max_iters, nullptr, only)
+                                          : refine<double>(nullptr, d, B, sp, s, outer, max_iters, nullptr, only);
 }
 
 double bench_spmv(mof_mesh *m, uint32_t precision, int32_t B, int32_t reps, hipStream_t s,
@@ -2462,54 +2395,29 @@ struct SysSwap {
     }
 };
 
-// mof_test_pcg_inner for one working type
+// ---- what mof_test_pcg_inner and mof_dd_test_pcg_inner share ----
+
+// a mesh of the hook holds the last solve's operator of V for B systems (and a built multigrid)
 template <typename V>
-void test_pcg_inner(mof_mesh *m, int32_t B, const double *rhs, double rtol, double outer_rtol, double etol, bool amg,
-                    int32_t max_iter, const uint8_t *active, int32_t *hint2, const uint32_t *sentinel, void *x,
-                    void *r, void *z, void *p, void *q, uint32_t *x0, double *scal, int32_t *sysi, double *sysd,
-                    void *dinv, int32_t a_system, void *A, int32_t *meta) {
-    constexpr bool f32 = sizeof(V) == 4;
-    Workspace &w = m->ws;
-    const size_t N = (size_t)m->N, nv = N * B, snb = (size_t)m->pat.sell_nb();
-    MOF_REQUIRE(B >= 1 && B <= w.cap && w.nblk > 0, "the handle's last batch had fewer systems");
-    MOF_REQUIRE(m->n_own == m->N, "a decomposed part's handle");
-    MOF_REQUIRE(max_iter >= 0, "negative iteration cap");
-    MOF_REQUIRE(!amg || f32, "the multigrid preconditions the fp32 inner solve only");
-    const V *Ap;
-    const V *dv;
-    if constexpr (f32) {
-        MOF_REQUIRE(w.A32.n >= 4 * snb * B, "no fp32 operator: the last solve was not mixed-precision");
-        Ap = w.A32.p;
-        dv = w.dinv32.p;
-    } else {
-        MOF_REQUIRE(w.A64.n >= 4 * snb * B, "no fp64 operator: the last solve was not an fp64 one");
-        Ap = w.A64.p;
-        dv = w.dinv64.p;
-    }
+void hook_require(const mof_mesh *m, int32_t B, bool amg) {
+    const Workspace &w = m->ws;
+    const size_t need = 4 * (size_t)m->pat.sell_nb() * B;
+    MOF_REQUIRE(B >= 1 && B <= w.cap && w.nblk > 0, "the handle's (a part's) last batch had fewer systems");
+    if constexpr (sizeof(V) == 4)
+        MOF_REQUIRE(w.A32.n >= need, "no fp32 operator: the last solve was not mixed-precision");
+    else
+        MOF_REQUIRE(w.A64.n >= need, "no fp64 operator: the last solve was not an fp64 one");
     if (amg) {
-        MOF_REQUIRE(m->amg && amg_levels(m) >= 2, "the handle has no built multigrid");
+        MOF_REQUIRE(m->amg && amg_levels(m) >= 2, "the handle (a part) has no built multigrid");
         MOF_REQUIRE(B <= amg_capacity(m), "the multigrid's storage holds fewer systems");
     }
-    MOF_REQUIRE(a_system < B, "bad system to read back");
-    hipStream_t s = m->stream;
-    MOF_HIP(hipStreamSynchronize(s));
-    DevArray<double> drhs;
-    drhs.alloc(2 * nv);
-    MOF_HIP(hipMemcpy(drhs.p, rhs, sizeof(double) * 2 * nv, hipMemcpyHostToDevice));
-    SysSwap swap(m, B, active);
-    float *x0p = amg ? amg_fine(m).x0 : nullptr;
-    if (sentinel) {
-        for (DevArray<double> *a : {&w.vx, &w.vr, &w.vz, &w.vp, &w.vq})
-            MOF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a->p), (int)*sentinel,
-                                      2 * nv * sizeof(V) / 4, s));
-        if (x0p) MOF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(x0p), (int)*sentinel, nv, s));
-    }
-    // partial records of systems that never run read as zero
-    MOF_HIP(hipMemsetAsync(w.part_pq.p, 0, sizeof(double) * 2 * w.nblk * B, s));
-    MOF_HIP(hipMemsetAsync(w.part_rzrr.p, 0, sizeof(double) * 4 * w.nblk * B, s));
-    MOF_HIP(hipMemsetAsync(w.sc.p, 0, sizeof(double) * 6 * B, s));
+}
+
+// the SolveParams of a hook's one inner solve
+template <typename V>
+SolveParams hook_params(bool amg, int32_t max_iter, double rtol, double etol) {
     SolveParams sp{};
-    sp.precision = f32 ? MOF_PREC_MIXED : MOF_PREC_F64;
+    sp.precision = sizeof(V) == 4 ? MOF_PREC_MIXED : MOF_PREC_F64;
     sp.block_jacobi = true;
     sp.time_spmv = false;
     sp.amg = amg;
@@ -2520,49 +2428,123 @@ void test_pcg_inner(mof_mesh *m, int32_t B, const double *rhs, double rtol, doub
     sp.etol = etol;
     sp.stall = amg ? kPcgStall : 0;
     sp.fail_at_max_iter = false;
-    std::vector<int32_t> hint(2 * kBulkHint, 0);
-    if (hint2) {
-        hint[0] = hint2[0];
-        hint[kBulkHint] = hint2[1];
+    return sp;
+}
+
+// before the solve: the sentinel word in every mesh's five vectors and
+// smoother x0; partial records of systems that never run, and of workgroups
+// past a part's own count, read as zero
+template <typename V>
+void hook_prepare(const Parts<V> &p, bool amg, const uint32_t *sentinel, hipStream_t s) {
+    for (mof_mesh *m : p.mesh) {
+        Workspace &w = m->ws;
+        const size_t nv = (size_t)m->N * p.B;
+        if (sentinel) {
+            for (DevArray<double> *a : {&w.vx, &w.vr, &w.vz, &w.vp, &w.vq})
+                MOF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a->p), (int)*sentinel,
+                                          2 * nv * sizeof(V) / 4, s));
+            if (amg) MOF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(amg_fine(m).x0), (int)*sentinel, nv, s));
+        }
+        MOF_HIP(hipMemsetAsync(w.sc.p, 0, sizeof(double) * 6 * p.B, s));
     }
-    int32_t max_iters = 0;
-    const MatArgs<V> mat = make_mat<V>(m, Ap);
-    const int64_t total = pcg<V>(m, B, mat, dv, drhs.p, rtol, sp, s, &max_iters, nullptr, hint.data(), amg,
-                                 outer_rtol, etol);
-    // both slots' scalars as the kernels form them: k_red_rzrr's and k_red_pq's reduction (reduce_sys)
-    // of the partial records the solve left, for every system
-    PcgArgs<V> a = make_args<V>(m, B, mat, dv);
+    const size_t rec = (size_t)p.P * p.B * p.nmax;
+    MOF_HIP(hipMemsetAsync(p.part_pq, 0, sizeof(double) * 2 * rec, s));
+    MOF_HIP(hipMemsetAsync(p.part_rzrr, 0, sizeof(double) * 4 * rec, s));
+}
+
+void hook_get(void *dst, size_t at, const void *src, size_t bytes) {
+    if (dst) MOF_HIP(hipMemcpy(static_cast<char *>(dst) + at, src, bytes, hipMemcpyDeviceToHost));
+}
+
+// after the solve: both slots' scalars as the kernels form them, k_red_rzrr's
+// and k_red_pq's reduction (reduce_sys) of the partial records the solve left
+// (all parts'), for every system, by the first mesh; scal[slot][b] = {r.z, |r|^2, p.q}
+template <typename V>
+void hook_scalars(PcgArgs<V> a, int32_t B, hipStream_t s, double *scal) {
+    a.sm = sys_all(B);
     for (int32_t slot = 0; slot < 2; ++slot) {
         k_red_rzrr<V><<<dim3((unsigned)B), kWG, 0, s>>>(a, slot);
         k_red_pq<V><<<dim3((unsigned)B), kWG, 0, s>>>(a, slot);
     }
     MOF_HIP(hipGetLastError());
     MOF_HIP(hipStreamSynchronize(s));
-    auto get = [&](void *dst, const void *src, size_t bytes) {
-        if (dst) MOF_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-    };
-    const bool zh = f32 && amg && amg_fine(m).regular;
-    get(x, w.vx.p, sizeof(V) * 2 * nv);
-    get(r, w.vr.p, sizeof(V) * 2 * nv);
-    get(z, w.vz.p, zh ? sizeof(uint32_t) * nv : sizeof(V) * 2 * nv);
-    get(p, w.vp.p, sizeof(V) * 2 * nv);
-    get(q, w.vq.p, sizeof(V) * 2 * nv);
-    if (x0p) get(x0, x0p, sizeof(uint32_t) * nv);
-    if (scal) {
-        std::vector<double> sc((size_t)6 * B);
-        get(sc.data(), w.sc.p, sizeof(double) * 6 * B);
-        for (int32_t slot = 0; slot < 2; ++slot)
-            for (int32_t b = 0; b < B; ++b) {
-                double *o = scal + 3 * ((size_t)slot * B + b);
-                o[0] = sc[2 * ((size_t)slot * B + b)];
-                o[1] = sc[2 * ((size_t)slot * B + b) + 1];
-                o[2] = sc[(size_t)4 * B + (size_t)slot * B + b];
-            }
+    if (!scal) return;
+    std::vector<double> sc((size_t)6 * B);
+    hook_get(sc.data(), 0, a.sc, sizeof(double) * 6 * B);
+    for (int32_t slot = 0; slot < 2; ++slot)
+        for (int32_t b = 0; b < B; ++b) {
+            double *o = scal + 3 * ((size_t)slot * B + b);
+            o[0] = sc[2 * ((size_t)slot * B + b)];
+            o[1] = sc[2 * ((size_t)slot * B + b) + 1];
+            o[2] = sc[(size_t)4 * B + (size_t)slot * B + b];
+        }
+}
+
+// where a hook copies the meshes' state to (null: skipped), one mesh after the other
+struct HookOut {
+    void *x, *r, *z, *p, *q;
+    int32_t *sysi;
+    double *sysd;
+    void *dinv, *A;
+    size_t ov = 0, os = 0, od = 0, oa = 0;  // bytes of vectors, rows of sysi / sysd, bytes of dinv, of A so far
+};
+// zh: z holds a bf16 pair per vertex
+template <typename V>
+void hook_read(mof_mesh *m, int32_t B, bool amg, bool zh, int32_t a_system, HookOut &o) {
+    const Workspace &w = m->ws;
+    const size_t nv = (size_t)m->N * B, snb = (size_t)m->pat.sell_nb(), vb = sizeof(V) * 2 * nv;
+    hook_get(o.x, o.ov, w.vx.p, vb);
+    hook_get(o.r, o.ov, w.vr.p, vb);
+    hook_get(o.z, o.ov, w.vz.p, zh ? sizeof(uint32_t) * nv : vb);
+    hook_get(o.p, o.ov, w.vp.p, vb);
+    hook_get(o.q, o.ov, w.vq.p, vb);
+    o.ov += vb;
+    hook_get(o.sysi, o.os * sizeof(int32_t), w.sysi.p, sizeof(int32_t) * kSysStride * B);
+    hook_get(o.sysd, o.os * sizeof(double), w.sysd.p, sizeof(double) * kSysStride * B);
+    o.os += (size_t)kSysStride * B;
+    if (!amg) hook_get(o.dinv, o.od, ws_dinv<V>(w), sizeof(V) * 4 * nv);
+    o.od += sizeof(V) * 4 * nv;
+    if (a_system >= 0) hook_get(o.A, o.oa, ws_A<V>(w) + 4 * snb * (size_t)a_system, sizeof(V) * 4 * snb);
+    o.oa += sizeof(V) * 4 * snb;
+}
+
+// mof_test_pcg_inner for one working type
+template <typename V>
+void test_pcg_inner(mof_mesh *m, int32_t B, const double *rhs, double rtol, double outer_rtol, double etol, bool amg,
+                    int32_t max_iter, const uint8_t *active, int32_t *hint2, const uint32_t *sentinel, void *x,
+                    void *r, void *z, void *p, void *q, uint32_t *x0, double *scal, int32_t *sysi, double *sysd,
+                    void *dinv, int32_t a_system, void *A, int32_t *meta) {
+    constexpr bool f32 = sizeof(V) == 4;
+    Workspace &w = m->ws;
+    const size_t nv = (size_t)m->N * B;
+    hook_require<V>(m, B, amg);
+    MOF_REQUIRE(m->n_own == m->N, "a decomposed part's handle");
+    MOF_REQUIRE(max_iter >= 0, "negative iteration cap");
+    MOF_REQUIRE(!amg || f32, "the multigrid preconditions the fp32 inner solve only");
+    MOF_REQUIRE(a_system < B, "bad system to read back");
+    hipStream_t s = m->stream;
+    MOF_HIP(hipStreamSynchronize(s));
+    DevArray<double> drhs;
+    drhs.alloc(2 * nv);
+    MOF_HIP(hipMemcpy(drhs.p, rhs, sizeof(double) * 2 * nv, hipMemcpyHostToDevice));
+    SysSwap swap(m, B, active);
+    Parts<V> parts(m, nullptr, B);
+    hook_prepare(parts, amg, sentinel, s);
+    const SolveParams sp = hook_params<V>(amg, max_iter, rtol, etol);
+    parts.fill_args(amg, sp.stall);
+    std::vector<int32_t> hint(2 * kBulkHint, 0);
+    if (hint2) {
+        hint[0] = hint2[0];
+        hint[kBulkHint] = hint2[1];
     }
-    get(sysi, w.sysi.p, sizeof(int32_t) * kSysStride * B);
-    get(sysd, w.sysd.p, sizeof(double) * kSysStride * B);
-    if (!amg) get(dinv, dv, sizeof(V) * 4 * nv);
-    if (a_system >= 0) get(A, Ap + 4 * snb * (size_t)a_system, sizeof(V) * 4 * snb);
+    int32_t max_iters = 0;
+    const double *drhs_p = drhs.p;
+    const int64_t total = pcg<V>(parts, &drhs_p, rtol, sp, s, &max_iters, nullptr, hint.data(), amg, outer_rtol, etol);
+    hook_scalars(parts.args[0], B, s, scal);
+    const bool zh = f32 && amg && amg_fine(m).regular;
+    HookOut out{x, r, z, p, q, sysi, sysd, dinv, A};
+    hook_read<V>(m, B, amg, zh, a_system, out);
+    if (amg) hook_get(x0, 0, amg_fine(m).x0, sizeof(uint32_t) * nv);
     if (hint2) {
         hint2[0] = hint[0];
         hint2[1] = hint[kBulkHint];
@@ -2570,7 +2552,7 @@ void test_pcg_inner(mof_mesh *m, int32_t B, const double *rhs, double rtol, doub
     if (meta) {
         const int32_t v[8] = {zh,
                               m->sym_reads,
-                              mat.sell_idx != nullptr,
+                              parts.args[0].mat.sell_idx != nullptr,
                               w.nblk <= kSelfRedBlk,
                               w.nblk,
                               (int32_t)std::min<int64_t>(total, INT32_MAX),
@@ -2587,117 +2569,42 @@ void test_pcg_dd_inner(mof_dd *d, int32_t B, const double *rhs, double rtol, boo
                        double *sysd, void *dinv, int32_t a_system, void *A, double *part_rzrr, double *part_pq,
                        double *scal, int32_t *meta) {
     constexpr bool f32 = sizeof(V) == 4;
-    const size_t L = d->parts.size();
     MOF_REQUIRE(d->rank < 0, "an in-process handle only");
     MOF_REQUIRE(B >= 1 && B <= d->cap && d->nmax > 0, "the handle's last batch had fewer systems");
     MOF_REQUIRE(max_iter >= 0, "negative iteration cap");
     MOF_REQUIRE(!amg || f32, "the multigrid preconditions the fp32 inner solve only");
     MOF_REQUIRE(a_system < B, "bad system to read back");
-    for (mof_mesh *m : d->parts) {
-        const Workspace &w = m->ws;
-        const size_t snb = (size_t)m->pat.sell_nb();
-        MOF_REQUIRE(B <= w.cap && w.nblk > 0, "a part's last batch had fewer systems");
-        if (f32)
-            MOF_REQUIRE(w.A32.n >= 4 * snb * B, "no fp32 operator: the last solve was not mixed-precision");
-        else
-            MOF_REQUIRE(w.A64.n >= 4 * snb * B, "no fp64 operator: the last solve was not an fp64 one");
-        if (amg) {
-            MOF_REQUIRE(m->amg && amg_levels(m) >= 2, "a part has no built multigrid");
-            MOF_REQUIRE(B <= amg_capacity(m), "a part's multigrid storage holds fewer systems");
-        }
-    }
+    for (const mof_mesh *m : d->parts) hook_require<V>(m, B, amg);
     hipStream_t s = d->stream;
     MOF_HIP(hipStreamSynchronize(s));
     std::vector<std::unique_ptr<DevKeep>> keep;
     std::vector<std::unique_ptr<SysSwap>> swap;
+    std::vector<const double *> drhs;
     size_t off = 0;
-    for (size_t l = 0; l < L; ++l) {
-        mof_mesh *m = d->parts[l];
+    for (mof_mesh *m : d->parts) {
         Workspace &w = m->ws;
         const size_t nv = (size_t)m->N * B;
         keep.emplace_back(new DevKeep(w.rhs.p, sizeof(double) * 2 * nv));
         MOF_HIP(hipMemcpy(w.rhs.p, rhs + off, sizeof(double) * 2 * nv, hipMemcpyHostToDevice));
+        drhs.push_back(w.rhs.p);
         off += 2 * nv;
         swap.emplace_back(new SysSwap(m, B, nullptr));
-        if (sentinel) {
-            for (DevArray<double> *a : {&w.vx, &w.vr, &w.vz, &w.vp, &w.vq})
-                MOF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(a->p), (int)*sentinel,
-                                          2 * nv * sizeof(V) / 4, s));
-            if (amg) MOF_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(amg_fine(m).x0), (int)*sentinel, nv, s));
-        }
-        MOF_HIP(hipMemsetAsync(w.sc.p, 0, sizeof(double) * 6 * B, s));
     }
-    // as solve_batch_dd: records of workgroups past a part's own count read as zero
-    MOF_HIP(hipMemsetAsync(d->part_pq.p, 0, d->part_pq.bytes(), s));
-    MOF_HIP(hipMemsetAsync(d->part_rzrr.p, 0, d->part_rzrr.bytes(), s));
-    SolveParams sp{};
-    sp.precision = f32 ? MOF_PREC_MIXED : MOF_PREC_F64;
-    sp.block_jacobi = true;
-    sp.time_spmv = false;
-    sp.amg = amg;
-    sp.max_iter = max_iter;
-    sp.max_outer = 1;
-    sp.rtol = rtol;
-    sp.inner_rtol = rtol;
-    sp.stall = amg ? kPcgStall : 0;
-    sp.fail_at_max_iter = false;
+    Parts<V> parts(nullptr, d, B);
+    hook_prepare(parts, amg, sentinel, s);
+    const SolveParams sp = hook_params<V>(amg, max_iter, rtol, 0.0);
+    parts.fill_args(amg, sp.stall);
     int32_t max_iters = 0, hint = 0;
-    const int64_t total = pcg_dd<V>(d, B, true, rtol, sp, s, &max_iters, &hint, amg);
-    // both slots' sums as part 0 forms them (k_red_rzrr, k_red_pq over the records of all parts)
-    std::vector<PcgArgs<V>> args = dd_args<V>(d, B, amg);
-    for (int32_t slot = 0; slot < 2; ++slot) {
-        k_red_rzrr<V><<<dim3((unsigned)B), kWG, 0, s>>>(args[0], slot);
-        k_red_pq<V><<<dim3((unsigned)B), kWG, 0, s>>>(args[0], slot);
-    }
-    MOF_HIP(hipGetLastError());
-    MOF_HIP(hipStreamSynchronize(s));
-    auto get = [&](void *dst, size_t at, const void *src, size_t bytes) {
-        if (dst) MOF_HIP(hipMemcpy(static_cast<char *>(dst) + at, src, bytes, hipMemcpyDeviceToHost));
-    };
-    size_t ov = 0, os = 0, od = 0, oa = 0;
-    for (size_t l = 0; l < L; ++l) {
-        mof_mesh *m = d->parts[l];
-        Workspace &w = m->ws;
-        const size_t nv = (size_t)m->N * B, snb = (size_t)m->pat.sell_nb(), vb = sizeof(V) * 2 * nv;
-        get(x, ov, w.vx.p, vb);
-        get(r, ov, w.vr.p, vb);
-        get(z, ov, w.vz.p, vb);
-        get(p, ov, w.vp.p, vb);
-        get(q, ov, w.vq.p, vb);
-        ov += vb;
-        get(sysi, os * sizeof(int32_t), w.sysi.p, sizeof(int32_t) * kSysStride * B);
-        get(sysd, os * sizeof(double), w.sysd.p, sizeof(double) * kSysStride * B);
-        os += (size_t)kSysStride * B;
-        const V *Ap, *dv;
-        if constexpr (f32) {
-            Ap = w.A32.p;
-            dv = w.dinv32.p;
-        } else {
-            Ap = w.A64.p;
-            dv = w.dinv64.p;
-        }
-        if (!amg) get(dinv, od, dv, sizeof(V) * 4 * nv);
-        od += sizeof(V) * 4 * nv;
-        if (a_system >= 0) get(A, oa, Ap + 4 * snb * (size_t)a_system, sizeof(V) * 4 * snb);
-        oa += sizeof(V) * 4 * snb;
-    }
+    const int64_t total = pcg<V>(parts, drhs.data(), rtol, sp, s, &max_iters, nullptr, &hint, amg);
+    hook_scalars(parts.args[0], B, s, scal);
+    HookOut out{x, r, z, p, q, sysi, sysd, dinv, A};
+    for (mof_mesh *m : d->parts) hook_read<V>(m, B, amg, false, a_system, out);
     const size_t rec = (size_t)d->P * B * d->nmax;
-    get(part_rzrr, 0, d->part_rzrr.p, sizeof(double) * 4 * rec);
-    get(part_pq, 0, d->part_pq.p, sizeof(double) * 2 * rec);
-    if (scal) {
-        std::vector<double> sc((size_t)6 * B);
-        get(sc.data(), 0, d->parts[0]->ws.sc.p, sizeof(double) * 6 * B);
-        for (int32_t slot = 0; slot < 2; ++slot)
-            for (int32_t b = 0; b < B; ++b) {
-                double *o = scal + 3 * ((size_t)slot * B + b);
-                o[0] = sc[2 * ((size_t)slot * B + b)];
-                o[1] = sc[2 * ((size_t)slot * B + b) + 1];
-                o[2] = sc[(size_t)4 * B + (size_t)slot * B + b];
-            }
-    }
+    hook_get(part_rzrr, 0, d->part_rzrr.p, sizeof(double) * 4 * rec);
+    hook_get(part_pq, 0, d->part_pq.p, sizeof(double) * 2 * rec);
     if (meta) {
         const int32_t v[6] = {d->nmax, d->P, (int32_t)std::min<int64_t>(total, INT32_MAX), max_iters, kSysStride,
-                              (int32_t)L};
+                              (int32_t)d->parts.size()};
         std::copy(v, v + 6, meta);
     }
 }

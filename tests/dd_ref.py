@@ -1,5 +1,5 @@
 """CPU restatement of the decomposed solve (csrc/mof_dd_plan.cpp, mof_dd.hip,
-pcg_dd of mof_pcg.hip) in fp64 numpy: the halo plan from its definition, the
+pcg() of mof_pcg.hip over the parts) in fp64 numpy: the halo plan from its definition, the
 halo exchange and the gather as copies, and the lockstep PCG iteration over
 the parts. tests/test_dd_ref.py checks it on the CPU, tests/test_gpu_dd_kernels.py
 holds the device to it.

@@ -1,6 +1,6 @@
 """The decomposed solve (config C5) below V: the halo plan, the halo and gather
 kernels of csrc/mof_dd.hip, the parts' operators, the lockstep inner iteration
-(pcg_dd of csrc/mof_pcg.hip) and the refinement step, against tests/dd_ref.py
+(pcg() of csrc/mof_pcg.hip over the parts) and the refinement step, against tests/dd_ref.py
 (the plan, copies, cross-part sums) and the derived bounds of tests/pcg_ref.py.
 Every assertion is byte equality or error / bound <= 1.0 of a derived bound:
 pcg_ref's and vcycle_ref's, and dd_ref's two for the fp32 assembly and the fp64
@@ -22,7 +22,7 @@ Cases (B = 3 systems):
   cap G2_cap641 (open, boundary sweeps), RCB, P = 3
   rnd random_sphere(1500), RCB, P = 3: every part reads plain (asserted)
 
-mof_dd_test_pcg_inner runs the production pcg_dd capped at K = 0, 1, ...: runs
+mof_dd_test_pcg_inner runs the production pcg() capped at K = 0, 1, ...: runs
 are bit-reproducible (asserted), so the state at cap K is the input of the
 transition cap K + 1 shows. Per part, pcg_ref.check_first / check_step run
 with nown; the three sums are shared by all parts and are checked once, over
@@ -531,7 +531,7 @@ def test_runs_reproducible_and_parts_agree(case, precond, precision):
         assert bytes_equal(o, d["caps"][K]), (case, precond, K)
     print(case, precond, precision, "steps to stop", d["conv"], "row blocks", d["nblk"], "nmax", d["caps"][0]["nmax"],
           "probe ran", d["ran_probe"], "cap 0 ran", d["ran_cap0"])
-    # cap 0: the FIRST instance alone, once per part (pcg_dd's check launch took the other one before)
+    # cap 0: the FIRST instance alone, once per part (the parts' check launch took the other one before)
     spmv0 = {k: n for k, n in d["ran_cap0"].items() if k.startswith("spmv")}
     assert len(spmv0) == 1 and "_first" in next(iter(spmv0)) and sum(spmv0.values()) == len(d["plan"]), spmv0
     assert "update" not in d["ran_cap0"] and "conv_early" not in d["ran_probe"]
@@ -586,7 +586,7 @@ def test_stop_rule_and_final_state(case, precond, precision):
 @pytest.mark.parametrize("case", ["a", "b", "e"])
 def test_multigrid_z_is_each_parts_cycle(case):
     """z_K is, on every part's owned rows, the output of mof_test_amg_vcycle on
-    that part's r_K, byte for byte, up to the step c a system stops at (pcg_dd
+    that part's r_K, byte for byte, up to the step c a system stops at (pcg()
     launches no k_pcg_conv_early: the cycle still runs on r_c, and SpMV c stops
     the system); after it z never changes again, ghost rows included. The
     cycle's ghost rows are never read: no sentinel word is left in z after the
@@ -687,7 +687,7 @@ def part_cycle(case, q):
 @pytest.mark.parametrize("case,q", [("a", 0), ("cap", 0), ("rnd", 1)])
 def test_part_vcycle(case, q):
     """The twelve stages of tests/test_gpu_vcycle.py (its checks, its bounds) on
-    one part's cycle, run as pcg_dd runs it: the ghost blocks of the read-back
+    one part's cycle, run as pcg() runs it on a part: the ghost blocks of the read-back
     level-0 copy are the identity, so the reference's ghost rows are decoupled
     too. The part cycle as a whole operator is symmetric to the level the single
     domain is held to (1e-12 of its norm) and positive definite on the owned
