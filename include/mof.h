@@ -578,9 +578,10 @@ int mof_test_amg_vcycle_tables(mof_mesh *mesh, int32_t level, int32_t system, in
                                int32_t *bsw_bsrc, uint32_t *bsw_A);
 /* Test hook: counts[0..25) = launches so far in this process of k_res0_ns
  * (plain / mirrored, packed), k_restrict<2,2>, k_restrict<3>,
- * k_restrict0_sa<2>, <3>, k_res3, k_subcycle, k_prolong<3>, k_prolong3_sa,
- * k_prolong0<1>, <2>, k_prolong0_sa<1>, <2>, k_post3, k_bsweep<false>, <true>,
- * and k_post0_ns<XM, ZH, 2, PK> at 17 + (XM - 1) * 4 + ZH * 2 + PK. */
+ * k_restrict0_sa<2>, <3>, k_res3, k_subcycle, k_prolong, k_prolong_sa<3,0,8>
+ * (slot 9), k_prolong0<1>, <2>, k_prolong_sa<2,1,16>, <2,2,16> (slots 12, 13),
+ * k_post3, k_bsweep<false>, <true>, and k_post0_ns<XM, ZH, 2, PK> at
+ * 17 + (XM - 1) * 4 + ZH * 2 + PK. */
 int mof_test_vcycle_launches(int64_t *counts);
 /* Test hook: the production inner PCG (pcg<V>() of mof_pcg.hip: its own
  * launches, grids, chunks and system map) on a given right-hand side, capped

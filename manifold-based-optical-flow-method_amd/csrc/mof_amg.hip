@@ -16,11 +16,12 @@
 //   level 0 pre-smooth x0 = w D^-1 r is fused into k_pcg_update / k_pcg_init;
 //   per level l:  k_res0 / k_res3  r_l = b_l - A_l x_l, written in member
 //                                  order of the next level's aggregates
-//                 k_restrict       b_{l+1} = Q^T r_l (contiguous members),
+//                 k_restrict / k_restrict0_sa  b_{l+1} = P^T r_l (tentative P:
+//                                  contiguous members; smoothed P: list entries),
 //                                  x_{l+1} = w1 D^-1 b_{l+1} (next pre-smooth)
 //   levels with <= kSubNodes nodes and the coarsest solve y = A_c^-1 b run in
 //   one launch (k_subcycle, one workgroup per system);
-//   per level l:  k_prolong0 / k_prolong  x_l += Q y_{l+1}
+//   per level l:  k_prolong0 / k_prolong / k_prolong_sa  x_l += P y_{l+1}
 //                 k_post0 / k_post3  y_l = x_l + w D^-1 (b_l - A_l x_l); at
 //                                  level 0 y = z and the partial r.z of the PCG
 // Every launch covers all B systems and skips retired systems. Level 0 sweeps
@@ -50,7 +51,9 @@ std::atomic<int> g_force_galerkin_ns{0};
 enum GalKernel { kGal0Ns, kGal0Ent, kGalSys2F32, kGalSys2Bf16, kGalSys3, kGal3Ns, kGal3Ent, kGal3Big, kGalKernels };
 std::atomic<int64_t> g_galerkin_launches[kGalKernels];
 // launches so far of each V-cycle kernel instance (mof_test_vcycle_launches),
-// in this order; k_post0_ns's eight from kVcPost0: (XM - 1) * 4 + ZH * 2 + PK
+// in this order; kVcProlong3Sa: k_prolong_sa<3, 0, kNS3>, kVcProlong0SaX1 /
+// X2: k_prolong_sa<2, 1 / 2, kNSP>; k_post0_ns's eight from kVcPost0:
+// (XM - 1) * 4 + ZH * 2 + PK
 enum VcKernel {
     kVcRes0, kVcRes0Pk, kVcRestrict2, kVcRestrict3, kVcRestrict0Sa2, kVcRestrict0Sa3, kVcRes3, kVcSubcycle,
     kVcProlong3, kVcProlong3Sa, kVcProlong0X1, kVcProlong0X2, kVcProlong0SaX1, kVcProlong0SaX2, kVcPost3,
@@ -111,8 +114,6 @@ __device__ __forceinline__ void ldm(const float *A, int64_t idx, float (&a)[BS][
         }
     }
 }
-template <int BS>
-constexpr int vstride() { return BS == 2 ? 2 : 4; }
 template <int BS>
 constexpr int bstride() { return BS == 2 ? 4 : kB3; }
 
@@ -880,17 +881,75 @@ __device__ __forceinline__ void res3_node(const Lvl &L, int32_t b, int32_t i) {
     stv<3>(L.r + vo, L.apos[i], ri);
 }
 
-// Level 0's restricted residual r1 stays in aggregate member order (k_res0
-// scatters into it): node order made k_res0's stores coalesced (1053 -> 961
-// us) but the restriction's member gathers scattered (233 -> 361 us), a net
-// loss (round 2, C3, B = 512).
+// The NS systems a workgroup or thread of a multi-system kernel carries:
+// slot t is logical system l0 + t of the launch (SysMap). b(t) is its system
+// (sm_b clamps a slot past the launch's last system to that one, so loads
+// stay in bounds); act(t): the slot is inside the launch and its system not
+// retired -- only those slots store.
+template <int NS>
+struct SysGroup {
+    const SysMap &sm;
+    const int32_t *sysi;
+    int32_t l0;
+    __device__ __forceinline__ int32_t b(int t) const { return sm_b(sm, l0 + t); }
+    __device__ __forceinline__ bool act(int t) const { return l0 + t < sm.n && !retired(sysi, b(t)); }
+    __device__ __forceinline__ bool any() const {
+        bool a = false;
+#pragma unroll
+        for (int t = 0; t < NS; ++t) a |= act(t);
+        return a;
+    }
+};
+
+// A restriction's finish: b_C[I] = acc; with smooth also the coarse level's
+// pre-smoothed iterate x_C[I] = w D_C^-1 b_C[I]. The same bits from every
+// caller, with fp contraction on or off: matvec contracts as it is defined
+// and the scaling is a single multiply.
+__device__ __forceinline__ void coarse_store(const Lvl &C, int32_t b, int32_t I, const float (&acc)[3], bool smooth,
+                                             float omega) {
+    const int64_t vo = (int64_t)b * C.n * 4;
+    stv<3>(C.b + vo, I, acc);
+    if (smooth) {
+        float d[3][3], x[3];
+        ld_dh(C, b, I, d);
+        matvec<3>(d, acc, x);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) x[c] *= omega;
+        stv<3>(C.x + vo, I, x);
+    }
+}
+
+// The iterate a prolongation corrects, node i of system b. Level 0 (BSF = 2)
+// reads the x0 word of F.x and writes the corrected pair back in that format
+// in place (XM = 1) or as float2 into F.y, full precision for the
+// post-smoothing (XM = 2, see AmgDevice::xm); a coarse level (BSF = 3) keeps
+// float4 rows in F.x.
 template <int BSF>
-__device__ __forceinline__ int32_t r_at(const Lvl &, int32_t q) {
-    return q;
+__device__ __forceinline__ void ld_xf(const Lvl &F, int32_t b, int32_t i, float (&x)[BSF]) {
+    if constexpr (BSF == 2) {
+        const float2 t = ld_x0(F.x, (int64_t)b * F.n + i);
+        x[0] = t.x;
+        x[1] = t.y;
+    } else {
+        ldv<3>(F.x + (int64_t)b * F.n * 4, i, x);
+    }
+}
+template <int BSF, int XM = 0>
+__device__ __forceinline__ void st_xf(const Lvl &F, int32_t b, int32_t i, const float (&x)[BSF]) {
+    if constexpr (BSF == 3)
+        stv<3>(F.x + (int64_t)b * F.n * 4, i, x);
+    else if constexpr (XM == 2)
+        reinterpret_cast<float2 *>(F.y)[(int64_t)b * F.n + i] = make_float2(x[0], x[1]);
+    else
+        st_x0(F.x, (int64_t)b * F.n + i, x[0], x[1]);
 }
 
 // b_C[I] = sum over the members of aggregate I of Q^T r (member order,
 // contiguous, U at a time); with smooth also x_C[I] = w D_C^-1 b_C[I].
+// Level 0's restricted residual r1 stays in aggregate member order too
+// (k_res0_ns scatters into it): node order made k_res0's stores coalesced
+// (1053 -> 961 us) but the restriction's member gathers scattered (233 ->
+// 361 us), a net loss (round 2, C3, B = 512).
 template <int BSF>
 __device__ __forceinline__ void restrict_node(const Lvl &F, const Lvl &C, int32_t b, int32_t I, bool smooth,
                                               float omega) {
@@ -900,7 +959,7 @@ __device__ __forceinline__ void restrict_node(const Lvl &F, const Lvl &C, int32_
     for (int32_t t0 = q0; t0 < q1; t0 += U) {
         float ri[U][BSF], qm[U][BSF * 3];
 #pragma unroll
-        for (int u = 0; u < U; ++u) ldr<BSF>(F.r, b, F.n, r_at<BSF>(F, min(t0 + u, q1 - 1)), ri[u]);
+        for (int u = 0; u < U; ++u) ldr<BSF>(F.r, b, F.n, min(t0 + u, q1 - 1), ri[u]);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const float *p = F.Qm + (int64_t)min(t0 + u, q1 - 1) * BSF * 3;
@@ -916,41 +975,18 @@ __device__ __forceinline__ void restrict_node(const Lvl &F, const Lvl &C, int32_
                 for (int c = 0; c < 3; ++c) acc[c] += qm[u][3 * k + c] * (on * ri[u][k]);
         }
     }
-    const int64_t vo = (int64_t)b * C.n * 4;
-    stv<3>(C.b + vo, I, acc);
-    if (smooth) {
-        float d[3][3], x[3];
-        ld_dh(C, b, I, d);
-        matvec<3>(d, acc, x);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) x[c] *= omega;
-        stv<3>(C.x + vo, I, x);
-    }
+    coarse_store(C, b, I, acc, smooth, omega);
 }
 
-// x_i += Q_i y_C[agg(i)]; level 0's corrected iterate in the x0 format in
-// place (XM = 1) or as float2 in F.y (XM = 2), see AmgDevice::xm
-template <int BSF, int XM = 2>
+// coarse level, tentative prolongator: x_i += Q_i y_C[agg(i)]
 __device__ __forceinline__ void prolong_node(const Lvl &F, const Lvl &C, int32_t b, int32_t i) {
-    float y[3], xi[BSF];
+    float y[3], xi[3];
     ldv<3>(C.y + (int64_t)b * C.n * 4, F.agg[i], y);
-    float *xb = F.x + (int64_t)b * F.n * vstride<BSF>();
-    if constexpr (BSF == 2) {
-        const float2 t = ld_x0(F.x, (int64_t)b * F.n + i);
-        xi[0] = t.x;
-        xi[1] = t.y;
-    } else {
-        ldv<BSF>(xb, i, xi);
-    }
-    const float *qi = F.Q + (int64_t)i * BSF * 3;
+    ld_xf<3>(F, b, i, xi);
+    const float *qi = F.Q + (int64_t)i * 9;
 #pragma unroll
-    for (int k = 0; k < BSF; ++k) xi[k] += qi[3 * k] * y[0] + qi[3 * k + 1] * y[1] + qi[3 * k + 2] * y[2];
-    if constexpr (BSF == 2 && XM == 2)  // full-precision x for the post-smoothing
-        reinterpret_cast<float2 *>(F.y)[(int64_t)b * F.n + i] = make_float2(xi[0], xi[1]);
-    else if constexpr (BSF == 2)
-        st_x0(F.x, (int64_t)b * F.n + i, xi[0], xi[1]);
-    else
-        stv<BSF>(xb, i, xi);
+    for (int k = 0; k < 3; ++k) xi[k] += qi[3 * k] * y[0] + qi[3 * k + 1] * y[1] + qi[3 * k + 2] * y[2];
+    st_xf<3>(F, b, i, xi);
 }
 
 // coarse level: y = x + w D^-1 (b - A x)
@@ -990,31 +1026,26 @@ constexpr int kRG = 1024;
 constexpr int kRestrS = 2;
 template <int BSF, int NS = 1>
 __global__ __launch_bounds__(kWG) void k_restrict(Lvl F, Lvl C, const int32_t *__restrict__ grp, int32_t ngrp,
-                                                  int32_t B, int32_t smooth, float omega,
-                                                  const int32_t *__restrict__ sysi) {
+                                                  int32_t smooth, float omega, const int32_t *__restrict__ sysi) {
     // no fp contraction: every system slot of the unrolled loops rounds alike
 #pragma clang fp contract(off)
     __shared__ float con[NS][3][kRG];
     int32_t g, bq;
     if (!xcd_map(ngrp, (F.sm.n + NS - 1) / NS, g, bq, kGrpRestr)) return;
-    const int32_t b0 = bq * NS;
-    bool any = false;
-#pragma unroll
-    for (int t = 0; t < NS; ++t) any |= b0 + t < F.sm.n && !retired(sysi, sm_b(F.sm, b0 + t));
-    if (!any) return;
+    const SysGroup<NS> sg{F.sm, sysi, bq * NS};
+    if (!sg.any()) return;
     const int32_t I0 = grp[g], I1 = grp[g + 1];
     const int32_t q0 = F.mptr[I0], q1 = F.mptr[I1];
     if (q1 - q0 > kRG) {  // one oversized aggregate
         if (threadIdx.x == 0)
             for (int t = 0; t < NS; ++t)
-                if (b0 + t < F.sm.n && !retired(sysi, sm_b(F.sm, b0 + t)))
-                    restrict_node<BSF>(F, C, sm_b(F.sm, b0 + t), I0, smooth != 0, omega);
+                if (sg.act(t)) restrict_node<BSF>(F, C, sg.b(t), I0, smooth != 0, omega);
         return;
     }
     for (int32_t q = q0 + threadIdx.x; q < q1; q += kWG) {
         float ri[NS][BSF];
 #pragma unroll
-        for (int t = 0; t < NS; ++t) ldr<BSF>(F.r, sm_b(F.sm, b0 + t), F.n, r_at<BSF>(F, q), ri[t]);
+        for (int t = 0; t < NS; ++t) ldr<BSF>(F.r, sg.b(t), F.n, q, ri[t]);
         const float *qm = F.Qm + (int64_t)q * BSF * 3;
         float qv[BSF * 3];
 #pragma unroll
@@ -1039,21 +1070,8 @@ __global__ __launch_bounds__(kWG) void k_restrict(Lvl F, Lvl C, const int32_t *_
 #pragma unroll
                 for (int c = 0; c < 3; ++c) acc[t][c] += con[t][c][q - q0];
 #pragma unroll
-        for (int t = 0; t < NS; ++t) {
-            if (b0 + t >= F.sm.n) continue;
-            const int32_t b = sm_b(F.sm, b0 + t);
-            if (retired(sysi, b)) continue;
-            const int64_t vo = (int64_t)b * C.n * 4;
-            stv<3>(C.b + vo, I, acc[t]);
-            if (smooth) {
-                float d[3][3], x[3];
-                ld_dh(C, b, I, d);
-                matvec<3>(d, acc[t], x);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) x[c] *= omega;
-                stv<3>(C.x + vo, I, x);
-            }
-        }
+        for (int t = 0; t < NS; ++t)
+            if (sg.act(t)) coarse_store(C, sg.b(t), I, acc[t], smooth, omega);
     }
 }
 
@@ -1089,7 +1107,7 @@ constexpr int kRGS = 512;  // list entries per restriction group (smoothed P)
 // (coarse node, system) per thread walking its list
 template <int BSF = 2>
 __global__ __launch_bounds__(kWG) void k_restrict0_sa(Lvl F, Lvl C, const int32_t *__restrict__ grp, int32_t ngrp,
-                                                      int32_t B, int32_t smooth, float omega,
+                                                      int32_t smooth, float omega,
                                                       const int32_t *__restrict__ sysi) {
     // no fp contraction: every system slot of the unrolled loops rounds alike
     // (a system's bits must not depend on its slot, i.e. on the batch split)
@@ -1098,11 +1116,8 @@ __global__ __launch_bounds__(kWG) void k_restrict0_sa(Lvl F, Lvl C, const int32_
     int32_t g, bq;
     const int32_t nq = (F.sm.n + kNSR - 1) / kNSR;
     if (!xcd_map(ngrp, nq, g, bq, kGrpRestr)) return;
-    const int32_t b0 = bq * kNSR;
-    bool any = false;
-#pragma unroll
-    for (int t = 0; t < kNSR; ++t) any |= b0 + t < F.sm.n && !retired(sysi, sm_b(F.sm, b0 + t));
-    if (!any) return;
+    const SysGroup<kNSR> sg{F.sm, sysi, bq * kNSR};
+    if (!sg.any()) return;
     const int32_t I0 = grp[g], I1 = grp[g + 1];
     const int32_t e0 = F.rptr[I0], e1 = F.rptr[I1];
     const bool big = e1 - e0 > kRGS;  // one coarse node with an oversized list: summed from memory
@@ -1114,7 +1129,7 @@ __global__ __launch_bounds__(kWG) void k_restrict0_sa(Lvl F, Lvl C, const int32_
         for (int k = 0; k < BSF * 3; ++k) pm[k] = p[k];
         float ri[kNSR][BSF];
 #pragma unroll
-        for (int t = 0; t < kNSR; ++t) ldr<BSF>(F.r, sm_b(F.sm, b0 + t), F.n, i, ri[t]);
+        for (int t = 0; t < kNSR; ++t) ldr<BSF>(F.r, sg.b(t), F.n, i, ri[t]);
 #pragma unroll
         for (int t = 0; t < kNSR; ++t)
 #pragma unroll
@@ -1151,9 +1166,7 @@ __global__ __launch_bounds__(kWG) void k_restrict0_sa(Lvl F, Lvl C, const int32_
     const int32_t nI = I1 - I0;
     for (int32_t q = threadIdx.x; q < nI * kNSR; q += kWG) {
         const int32_t t = q / nI, I = I0 + q - t * nI;
-        if (b0 + t >= F.sm.n) continue;
-        const int32_t b = sm_b(F.sm, b0 + t);
-        if (retired(sysi, b)) continue;
+        if (!sg.act(t)) continue;
         float acc[3] = {};
         for (int32_t e = F.rptr[I]; e < F.rptr[I + 1]; ++e) {
             float c3[3];
@@ -1169,172 +1182,93 @@ __global__ __launch_bounds__(kWG) void k_restrict0_sa(Lvl F, Lvl C, const int32_
 #pragma unroll
             for (int c = 0; c < 3; ++c) acc[c] += c3[c];
         }
-        const int64_t vo = (int64_t)b * C.n * 4;
-        stv<3>(C.b + vo, I, acc);
-        if (smooth) {
-            float d[3][3], x[3];
-            ld_dh(C, b, I, d);
-            matvec<3>(d, acc, x);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) x[c] *= omega;
-            stv<3>(C.x + vo, I, x);
-        }
+        coarse_store(C, sg.b(t), I, acc, smooth, omega);
     }
 }
 
-// Level 0 with a smoothed prolongator: x_i = x0_i + sum_k P_ik y_C[pcol k],
-// kNSP systems per thread (the row's P blocks and columns loaded once)
-template <int XM>
-__global__ __launch_bounds__(kWG) void k_prolong0_sa(Lvl F, Lvl C, int32_t nblk, int32_t B,
-                                                     const int32_t *__restrict__ sysi) {
+// Smoothed prolongator: x_i += sum over the fine node's P blocks of
+// P_ik y_C[pcol k]; NS systems per thread share the row's P blocks and
+// columns, each loaded once. Level 0 (BSF = 2, NS = kNSP; the measurements
+// above kNSR): x0_i read as the x0 word, the sum stored in the XM format
+// (st_xf). Level 1 (BSF = 3, NS = kNS3, AmgParams::smooth1): float4 rows in
+// place (round 5, F3: 559 us per 1024-system launch with one system per
+// thread).
+constexpr int kNS3 = 8;
+template <int BSF, int XM, int NS>
+__global__ __launch_bounds__(kWG) void k_prolong_sa(Lvl F, Lvl C, int32_t nblk, const int32_t *__restrict__ sysi) {
     // no fp contraction: every system slot of the unrolled loops rounds alike
     // (a system's bits must not depend on its slot, i.e. on the batch split)
 #pragma clang fp contract(off)
     int32_t rb, bq;
-    const int32_t nq = (F.sm.n + kNSP - 1) / kNSP;
-    if (!xcd_map(nblk, nq, rb, bq, kGrpProl)) return;
-    const int32_t b0 = bq * kNSP;
+    if (!xcd_map(nblk, (F.sm.n + NS - 1) / NS, rb, bq, kGrpProl)) return;
+    const SysGroup<NS> sg{F.sm, sysi, bq * NS};
     const int32_t i = rb * kWG + threadIdx.x;
     if (i >= F.n) return;
-    float x[kNSP][2];
+    float x[NS][BSF];
 #pragma unroll
-    for (int t = 0; t < kNSP; ++t) {
-        const float2 v = ld_x0(F.x, (int64_t)sm_b(F.sm, b0 + t) * F.n + i);
-        x[t][0] = v.x;
-        x[t][1] = v.y;
-    }
+    for (int t = 0; t < NS; ++t) ld_xf<BSF>(F, sg.b(t), i, x[t]);
     const int32_t k0 = F.pptr[i], k1 = F.pptr[i + 1];
     for (int32_t k = k0; k < k1; ++k) {
         const int32_t K = F.pcol[k];
-        const float *q = F.Q + (int64_t)k * 6;
-        float qm[6];
+        const float *p = F.Q + (int64_t)k * (BSF * 3);
+        float pm[BSF * 3];
 #pragma unroll
-        for (int c = 0; c < 6; ++c) qm[c] = q[c];
-        float y[kNSP][3];
+        for (int c = 0; c < BSF * 3; ++c) pm[c] = p[c];
+        float y[NS][3];
 #pragma unroll
-        for (int t = 0; t < kNSP; ++t) ldv<3>(C.y + (int64_t)sm_b(F.sm, b0 + t) * C.n * 4, K, y[t]);
+        for (int t = 0; t < NS; ++t) ldv<3>(C.y + (int64_t)sg.b(t) * C.n * 4, K, y[t]);
 #pragma unroll
-        for (int t = 0; t < kNSP; ++t) {
-            x[t][0] += qm[0] * y[t][0] + qm[1] * y[t][1] + qm[2] * y[t][2];
-            x[t][1] += qm[3] * y[t][0] + qm[4] * y[t][1] + qm[5] * y[t][2];
-        }
+        for (int t = 0; t < NS; ++t)
+#pragma unroll
+            for (int r = 0; r < BSF; ++r) x[t][r] += pm[3 * r] * y[t][0] + pm[3 * r + 1] * y[t][1] + pm[3 * r + 2] * y[t][2];
     }
 #pragma unroll
-    for (int t = 0; t < kNSP; ++t) {
-        if (b0 + t >= F.sm.n) continue;
-        const int32_t b = sm_b(F.sm, b0 + t);
-        if (retired(sysi, b)) continue;
-        if constexpr (XM == 2)  // full-precision x for the post-smoothing
-            reinterpret_cast<float2 *>(F.y)[(int64_t)b * F.n + i] = make_float2(x[t][0], x[t][1]);
-        else
-            st_x0(F.x, (int64_t)b * F.n + i, x[t][0], x[t][1]);
-    }
+    for (int t = 0; t < NS; ++t)
+        if (sg.act(t)) st_xf<BSF, XM>(F, sg.b(t), i, x[t]);
 }
 
-// x_i += sum over the fine node's P blocks of P_ik y_C[pcol k] (level 1,
-// smoothed prolongator), in place; kNS3 systems per thread share the row's P
-// blocks and columns (round 5, F3: 559 us per 1024-system launch with one
-// system per thread)
-constexpr int kNS3 = 8;
-__global__ __launch_bounds__(kWG) void k_prolong3_sa(Lvl F, Lvl C, int32_t nblk, int32_t B,
-                                                     const int32_t *__restrict__ sysi) {
-#pragma clang fp contract(off)
-    int32_t rb, bq;
-    if (!xcd_map(nblk, (F.sm.n + kNS3 - 1) / kNS3, rb, bq, kGrpProl)) return;
-    const int32_t i = rb * kWG + threadIdx.x;
-    if (i >= F.n) return;
-    const int32_t b0 = bq * kNS3;
-    float x[kNS3][3];
-#pragma unroll
-    for (int t = 0; t < kNS3; ++t) ldv<3>(F.x + (int64_t)sm_b(F.sm, b0 + t) * F.n * 4, i, x[t]);
-    for (int32_t k = F.pptr[i]; k < F.pptr[i + 1]; ++k) {
-        const float *p = F.Q + (int64_t)k * 9;
-        float pm[9];
-#pragma unroll
-        for (int c = 0; c < 9; ++c) pm[c] = p[c];
-        const int32_t K = F.pcol[k];
-        float y[kNS3][3];
-#pragma unroll
-        for (int t = 0; t < kNS3; ++t) ldv<3>(C.y + (int64_t)sm_b(F.sm, b0 + t) * C.n * 4, K, y[t]);
-#pragma unroll
-        for (int t = 0; t < kNS3; ++t)
-#pragma unroll
-            for (int r = 0; r < 3; ++r) x[t][r] += pm[3 * r] * y[t][0] + pm[3 * r + 1] * y[t][1] + pm[3 * r + 2] * y[t][2];
-    }
-#pragma unroll
-    for (int t = 0; t < kNS3; ++t) {
-        if (b0 + t >= F.sm.n) continue;
-        const int32_t b = sm_b(F.sm, b0 + t);
-        if (retired(sysi, b)) continue;
-        stv<3>(F.x + (int64_t)b * F.n * 4, i, x[t]);
-    }
-}
-
-template <int BSF>
+// coarse level, tentative prolongator: one (node, system) per thread
 __global__ __launch_bounds__(kWG) void k_prolong(Lvl F, Lvl C, const int32_t *__restrict__ sysi) {
     const int32_t i = blockIdx.x * kWG + threadIdx.x, b = sm_b(F.sm, blockIdx.y);
     if (i >= F.n || retired(sysi, b)) return;
-    prolong_node<BSF>(F, C, b, i);
+    prolong_node(F, C, b, i);
 }
 
-// Level 0 with the XCD-aware (node block, system) order: the B systems of a
-// node block run back to back on one XCD and share its Q rows in L2 instead
-// of re-reading Q per system (183 vs 261 us per 256-system launch with the
-// system-major grid; the coarse levels' kernels measured slower this way).
-// kProlR nodes x kProlS systems per thread, every load of the batch issued
-// before the first store: one node of one system per thread left each wave a
-// dependent agg -> y gather and little else (latency-bound), and the
-// systems of a thread share the node's agg and Q row loads. C3, 512
-// systems: 314 us (1 x 1), 270 (4 nodes), 231 (2 x 2), 202 (1 x 4), 210 (1 x 8)
-constexpr int kProlR = 1, kProlS = 4;
+// Level 0, tentative prolongator, with the XCD-aware (node block, system)
+// order: the B systems of a node block run back to back on one XCD and share
+// its Q rows in L2 instead of re-reading Q per system (183 vs 261 us per
+// 256-system launch with the system-major grid; the coarse levels' kernels
+// measured slower this way). One node of kProlS systems per thread, every
+// load of the batch issued before the first store: one node of one system per
+// thread left each wave a dependent agg -> y gather and little else
+// (latency-bound), and the systems of a thread share the node's agg and Q row
+// loads. C3, 512 systems, nodes x systems per thread: 314 us (1 x 1), 270
+// (4 x 1), 231 (2 x 2), 202 (1 x 4), 210 (1 x 8)
+constexpr int kProlS = 4;
 template <int XM>
-__global__ __launch_bounds__(kWG) void k_prolong0(Lvl F, Lvl C, int32_t nblk, int32_t B,
-                                                  const int32_t *__restrict__ sysi) {
+__global__ __launch_bounds__(kWG) void k_prolong0(Lvl F, Lvl C, int32_t nblk, const int32_t *__restrict__ sysi) {
     // no fp contraction: every system slot of the unrolled loops rounds alike
 #pragma clang fp contract(off)
     int32_t rb, bq;
     if (!xcd_map(nblk, (F.sm.n + kProlS - 1) / kProlS, rb, bq, kGrpProl)) return;
-    const int32_t n = F.n;
-    int32_t ii[kProlR], ag[kProlR];
-    float q[kProlR][6];
+    const SysGroup<kProlS> sg{F.sm, sysi, bq * kProlS};
+    const int32_t ii = rb * kWG + threadIdx.x, i = min(ii, F.n - 1);  // a lane past the last node loads that one
+    const int32_t ag = F.agg[i];
+    float q[6];
 #pragma unroll
-    for (int r = 0; r < kProlR; ++r) {
-        ii[r] = (rb * kProlR + r) * kWG + threadIdx.x;
-        const int32_t i = min(ii[r], n - 1);
-        ag[r] = F.agg[i];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) q[r][k] = F.Q[(int64_t)i * 6 + k];
-    }
-    float2 x0[kProlS][kProlR];
-    float y[kProlS][kProlR][3];
+    for (int k = 0; k < 6; ++k) q[k] = F.Q[(int64_t)i * 6 + k];
+    float x[kProlS][2], y[kProlS][3];
 #pragma unroll
     for (int t = 0; t < kProlS; ++t) {
-        const int32_t b = sm_b(F.sm, bq * kProlS + t);
-        const float *yb = C.y + (int64_t)b * C.n * 4;
-#pragma unroll
-        for (int r = 0; r < kProlR; ++r) {
-            x0[t][r] = ld_x0(F.x, (int64_t)b * n + min(ii[r], n - 1));
-            ldv<3>(yb, ag[r], y[t][r]);
-        }
+        ld_xf<2>(F, sg.b(t), i, x[t]);
+        ldv<3>(C.y + (int64_t)sg.b(t) * C.n * 4, ag, y[t]);
     }
 #pragma unroll
     for (int t = 0; t < kProlS; ++t) {
-        if (bq * kProlS + t >= F.sm.n) continue;
-        const int32_t b = sm_b(F.sm, bq * kProlS + t);
-        if (retired(sysi, b)) continue;
-        const int64_t vb = (int64_t)b * n;
+        if (!sg.act(t) || ii >= F.n) continue;
 #pragma unroll
-        for (int r = 0; r < kProlR; ++r) {
-            if (ii[r] >= n) break;
-            float xi[2] = {x0[t][r].x, x0[t][r].y};
-#pragma unroll
-            for (int k = 0; k < 2; ++k)
-                xi[k] += q[r][3 * k] * y[t][r][0] + q[r][3 * k + 1] * y[t][r][1] + q[r][3 * k + 2] * y[t][r][2];
-            if constexpr (XM == 2)  // full-precision x for the post-smoothing
-                reinterpret_cast<float2 *>(F.y)[vb + ii[r]] = make_float2(xi[0], xi[1]);
-            else
-                st_x0(F.x, vb + ii[r], xi[0], xi[1]);
-        }
+        for (int k = 0; k < 2; ++k) x[t][k] += q[3 * k] * y[t][0] + q[3 * k + 1] * y[t][1] + q[3 * k + 2] * y[t][2];
+        st_xf<2, XM>(F, sg.b(t), ii, x[t]);
     }
 }
 
@@ -1414,7 +1348,7 @@ __global__ __launch_bounds__(kSubWG) void k_subcycle(SubArgs a) {
     // up
     for (int32_t l = a.last - 1; l >= a.first; --l) {
         const Lvl &F = a.lv[l], &C = a.lv[l + 1];
-        for (int32_t i = tid; i < F.n; i += kSubWG) prolong_node<3>(F, C, b, i);
+        for (int32_t i = tid; i < F.n; i += kSubWG) prolong_node(F, C, b, i);
         __syncthreads();
         for (int32_t i = tid; i < F.n; i += kSubWG) post3_node(F, b, i, a.omega);
         __syncthreads();
@@ -1429,7 +1363,7 @@ __global__ __launch_bounds__(kSubWG) void k_subcycle(SubArgs a) {
 // the plain and the mirrored 32-bit tables; the launcher picks the instance.
 constexpr int kRes0NS = 2, kRes0U = kSweepU;
 template <int NS, bool PK>
-__global__ __launch_bounds__(kWG) MOF_ROW_OCC void k_res0_ns(int32_t N, int32_t nblk, int32_t B, SysMap sm, MatH mat,
+__global__ __launch_bounds__(kWG) MOF_ROW_OCC void k_res0_ns(int32_t N, int32_t nblk, SysMap sm, MatH mat,
                                                  const float *__restrict__ rv, const float *__restrict__ xv,
                                                  const int32_t *__restrict__ apos,
                                                  const int32_t *__restrict__ sysi, float *__restrict__ r1) {
@@ -2367,82 +2301,80 @@ void amg_vcycle(mof_mesh *m, int32_t B, const float *r0, float *z0, double *part
     // the cycle below level 0 from level 1's restricted b and pre-smoothed
     // x: down (residual, restriction + next pre-smooth), the fused tiny
     // levels, up (prolongation, post-smoothing into y)
+    const bool xm2 = G.xm == 2;
+    // b_{l+1} = P_l^T r_l and level l + 1's pre-smooth (the coarsest level has
+    // none): tentative or smoothed P, level 0 (BSF = 2) or a coarse level
+    auto launch_restrict = [&](int32_t l) {
+        const AmgDevLevel &D = G.lv[l];
+        const int32_t ns = D.smoothed ? kNSR : l == 0 ? kRestrS : 1;  // systems per workgroup
+        ++g_vcycle_launches[D.smoothed ? (l == 0 ? kVcRestrict0Sa2 : kVcRestrict0Sa3)
+                                       : (l == 0 ? kVcRestrict2 : kVcRestrict3)];
+        (D.smoothed ? (l == 0 ? k_restrict0_sa<2> : k_restrict0_sa<3>) : (l == 0 ? k_restrict<2, kRestrS> : k_restrict<3>))
+            <<<dim3(xcd_grid(D.ngrp, (nL + ns - 1) / ns, kGrpRestr)), kWG, 0, s>>>(v[l], v[l + 1], D.rgrp.p, D.ngrp,
+                                                                                   l + 1 < L - 1, om1, sysi);
+    };
+    // x_l += P_l y_{l+1}; level 0 writes the corrected iterate in the xm format
+    auto launch_prolong = [&](int32_t l) {
+        const AmgDevLevel &D = G.lv[l];
+        if (l > 0 && !D.smoothed) {
+            ++g_vcycle_launches[kVcProlong3];
+            k_prolong<<<grid2(v[l].n, nL), kWG, 0, s>>>(v[l], v[l + 1], sysi);
+            return;
+        }
+        const int32_t ns = l > 0 ? kNS3 : D.smoothed ? kNSP : kProlS;  // systems per thread
+        const int32_t nb = (v[l].n + kWG - 1) / kWG;
+        ++g_vcycle_launches[l > 0 ? kVcProlong3Sa : (D.smoothed ? kVcProlong0SaX1 : kVcProlong0X1) + (xm2 ? 1 : 0)];
+        (l > 0 ? k_prolong_sa<3, 0, kNS3>
+               : D.smoothed ? (xm2 ? k_prolong_sa<2, 2, kNSP> : k_prolong_sa<2, 1, kNSP>)
+                            : (xm2 ? k_prolong0<2> : k_prolong0<1>))
+            <<<dim3(xcd_grid(nb, (nL + ns - 1) / ns, kGrpProl)), kWG, 0, s>>>(v[l], v[l + 1], nb, sysi);
+    };
     auto coarse = [&]() {
         for (int32_t l = 1; l < S; ++l) {
-            const int32_t smooth = l + 1 < L - 1;
             k_res3<<<grid2(v[l].n, nL), kWG, 0, s>>>(v[l], sysi);
             ++g_vcycle_launches[kVcRes3];
-            ++g_vcycle_launches[G.lv[l].smoothed ? kVcRestrict0Sa3 : kVcRestrict3];
-            if (G.lv[l].smoothed)
-                k_restrict0_sa<3><<<dim3(xcd_grid(G.lv[l].ngrp, (nL + kNSR - 1) / kNSR, kGrpRestr)), kWG, 0, s>>>(
-                    v[l], v[l + 1], G.lv[l].rgrp.p, G.lv[l].ngrp, B, smooth, om1, sysi);
-            else
-                k_restrict<3><<<dim3(xcd_grid(G.lv[l].ngrp, nL, kGrpRestr)), kWG, 0, s>>>(
-                    v[l], v[l + 1], G.lv[l].rgrp.p, G.lv[l].ngrp, B, smooth, om1, sysi);
+            launch_restrict(l);
         }
         subcycle(S);
         for (int32_t l = S - 1; l >= 1; --l) {
-            ++g_vcycle_launches[G.lv[l].smoothed ? kVcProlong3Sa : kVcProlong3];
+            launch_prolong(l);
             ++g_vcycle_launches[kVcPost3];
-            if (G.lv[l].smoothed) {
-                const int32_t nb = (v[l].n + kWG - 1) / kWG;
-                k_prolong3_sa<<<dim3(xcd_grid(nb, (nL + kNS3 - 1) / kNS3, kGrpProl)), kWG, 0, s>>>(v[l], v[l + 1], nb,
-                                                                                                   B, sysi);
-            }
-            else
-                k_prolong<3><<<grid2(v[l].n, nL), kWG, 0, s>>>(v[l], v[l + 1], sysi);
             k_post3<<<grid2(v[l].n, nL), kWG, 0, s>>>(v[l], om1, sysi);
         }
     };
     // down at level 0: residual of the pre-smoothed x, restriction (+ level
     // 1's pre-smooth)
     {
-        const int32_t smooth = 1 < L - 1;
         if (G.bsw_n > 0) launch_bsweep<false>(G, sm, r0, v[0].x, om, sysi, s);
         tap_x(1, v[0].x, 1);
         ++g_vcycle_launches[mat0.sell_idx ? kVcRes0Pk : kVcRes0];
-        ++g_vcycle_launches[G.lv[0].smoothed ? kVcRestrict0Sa2 : kVcRestrict2];
         const dim3 gr(xcd_grid(nblk, (nL + kRes0NS - 1) / kRes0NS, kGrpSmooth > kRes0NS ? kGrpSmooth / kRes0NS : 1));
         (mat0.sell_idx ? k_res0_ns<kRes0NS, true> : k_res0_ns<kRes0NS, false>)<<<gr, kWG, 0, s>>>(
-            v[0].n, nblk, B, sm, mat0, r0, v[0].x, G.lv[0].smoothed ? nullptr : v[0].apos, sysi, v[0].r);
-        if (G.lv[0].smoothed) {
-            k_restrict0_sa<2><<<dim3(xcd_grid(G.lv[0].ngrp, (nL + kNSR - 1) / kNSR, kGrpRestr)), kWG, 0, s>>>(
-                v[0], v[1], G.lv[0].rgrp.p, G.lv[0].ngrp, B, smooth, om1, sysi);
-        } else {
-            k_restrict<2, kRestrS><<<dim3(xcd_grid(G.lv[0].ngrp, (nL + kRestrS - 1) / kRestrS, kGrpRestr)), kWG, 0, s>>>(
-                v[0], v[1], G.lv[0].rgrp.p, G.lv[0].ngrp, B, smooth, om1, sysi);
-        }
+            v[0].n, nblk, sm, mat0, r0, v[0].x, G.lv[0].smoothed ? nullptr : v[0].apos, sysi, v[0].r);
+        launch_restrict(0);
     }
     if (S == 1)  // level 1 is already one of the fused tiny levels
         subcycle(1);
     else
         coarse();
-    // up at level 0: coarse correction, post-smooth
+    // up at level 0: coarse correction, post-smooth, on the corrected iterate
+    // -- float2 in y (xm = 2), or the x0 word in place
     {
-        const int32_t nb0 = (v[0].n + kWG - 1) / kWG;
-        const int32_t nb0p = (v[0].n + kWG * kProlR - 1) / (kWG * kProlR);
-        const dim3 gsa(xcd_grid(nb0, (nL + kNSP - 1) / kNSP, kGrpProl)), gp(xcd_grid(nb0p, (nL + kProlS - 1) / kProlS, kGrpProl));
+        float *x = xm2 ? v[0].y : v[0].x;
+        const size_t words = xm2 ? 2 : 1;  // per vertex
         const bool packed = mat0.sell_idx != nullptr;
-        ++g_vcycle_launches[(G.lv[0].smoothed ? kVcProlong0SaX1 : kVcProlong0X1) + (G.xm == 2 ? 1 : 0)];
-        if (G.xm == 2) {
-            if (G.lv[0].smoothed)
-                k_prolong0_sa<2><<<gsa, kWG, 0, s>>>(v[0], v[1], nb0, B, sysi);
-            else
-                k_prolong0<2><<<gp, kWG, 0, s>>>(v[0], v[1], nb0p, B, sysi);
-            tap_x(2, v[0].y, 2);
-            if (G.bsw_n > 0) launch_bsweep<true>(G, sm, r0, v[0].y, om, sysi, s);
-            tap_x(3, v[0].y, 2);
-            launch_post0<2>(zh, packed, nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, v[0].y, om, sysi, z0, part_slot, rd);
-        } else {
-            if (G.lv[0].smoothed)
-                k_prolong0_sa<1><<<gsa, kWG, 0, s>>>(v[0], v[1], nb0, B, sysi);
-            else
-                k_prolong0<1><<<gp, kWG, 0, s>>>(v[0], v[1], nb0p, B, sysi);
-            tap_x(2, v[0].x, 1);
-            if (G.bsw_n > 0) launch_bsweep<false>(G, sm, r0, v[0].x, om, sysi, s);
-            tap_x(3, v[0].x, 1);
-            launch_post0<1>(zh, packed, nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, v[0].x, om, sysi, z0, part_slot, rd);
-        }
+        launch_prolong(0);
+        tap_x(2, x, words);
+        if (G.bsw_n > 0) (xm2 ? launch_bsweep<true> : launch_bsweep<false>)(G, sm, r0, x, om, sysi, s);
+        tap_x(3, x, words);
+        auto post0 = [&](auto xm) {
+            launch_post0<decltype(xm)::value>(zh, packed, nblk, nL, s, v[0].n, nblk, B, sm, mat0, r0, x, om, sysi, z0,
+                                              part_slot, rd);
+        };
+        if (xm2)
+            post0(std::integral_constant<int, 2>());
+        else
+            post0(std::integral_constant<int, 1>());
     }
     MOF_HIP(hipGetLastError());
 }

@@ -12,7 +12,7 @@ Each system gets another r: 0 a seeded normal vector scaled to the system's
 right-hand side, 1 zero (z must be exactly zero), 2 the right-hand side
 itself (batches of 5, and flat7, whose right-hand side cancels too much in
 stage 3: another normal vector), 3 the right-hand side, 4 an impulse at one
-vertex (a boundary vertex on an open mesh).
+vertex (a boundary vertex on an open mesh), 5 and up further normal vectors.
 
 The chain (stage_checks): the taps and the end state lead from r to z without
 a gap, every stage's reference is computed from the buffers the previous
@@ -51,11 +51,11 @@ Largest error / bound per kernel instance seen on an MI355X
 bf16 ulp), at most 1 by the window):
   pre-smooth 1.00   k_bsweep<false> 1.00   k_bsweep<true> 0.03
   k_res0_ns 1.00 (plain), 1.00 (packed)   k_restrict<2,2> 0.19   k_restrict<3> 0.13
-  k_restrict0_sa<2> 0.11   k_restrict0_sa<3> 0.02   k_res3 0.08   k_post3 0.07
+  k_restrict0_sa<2> 0.12   k_restrict0_sa<3> 0.02   k_res3 0.08   k_post3 0.07
   k_subcycle 0.10 (restriction) 0.11 (residual) 0.11 (coarsest solve)
              0.49 (prolongation) 0.07 (post-smoothing)
-  k_prolong<3> 0.44   k_prolong3_sa 0.26   k_prolong0<1> 1.00   k_prolong0<2> 0.46
-  k_prolong0_sa<1> 1.00   k_prolong0_sa<2> 0.44
+  k_prolong 0.44   k_prolong_sa<3,0,8> 0.26   k_prolong0<1> 1.00   k_prolong0<2> 0.46
+  k_prolong_sa<2,1,16> 1.00   k_prolong_sa<2,2,16> 0.44
   k_post0_ns with float2 z 0.08 .. 0.14, with bf16 z 1.00 (four instances each)
   r.z partials <= 0.005
 and at most 3.1 % of a stage's bf16 windows span two values (stage 3).
@@ -73,12 +73,19 @@ test_stored_operators_symmetric hold both.
 Every instance amg_vcycle can launch runs in some case, and each case
 asserts its own (the launch counters, mof_test_vcycle_launches): both
 k_res0_ns, k_restrict<2,2>, <3>, k_restrict0_sa<2>, <3>, k_res3, k_subcycle,
-k_prolong<3>, k_prolong3_sa, k_prolong0<1>, <2>, k_prolong0_sa<1>, <2>,
-k_post3, both k_bsweep and all eight k_post0_ns<XM, ZH, 2, PK> (the forced z
-format gives each mesh its second one; the unpacked XM = 1 pair needs the
-32-bit index tables forced on a regular mesh, G1_ico642_index32). k_to_h0 is
-not reachable: every multigrid solve's assembly writes the bf16 copy itself
-(DESIGN.md section 7).
+k_prolong (counter prolong3), k_prolong_sa<3,0,8> (prolong3_sa), k_prolong0<1>,
+<2>, k_prolong_sa<2,1,16>, <2,2,16> (prolong0_sa_x1, _x2), k_post3, both
+k_bsweep and all eight k_post0_ns<XM, ZH, 2, PK> (the forced z format gives
+each mesh its second one; the unpacked XM = 1 pair needs the 32-bit index
+tables forced on a regular mesh, G1_ico642_index32). Two cases fill the
+multi-system groups (SysGroup): G1_ico642_smoothed_b17's 17 systems make one
+full 16-system prolongation group and two full 8-system restriction groups,
+each beside a group of one, hull_chain_b9's 9 one full group of 8 and a group
+of one in level 1's smoothed transfers (G1_ico642 records 16 frames: the b17
+case takes the golden mesh under the synthetic travelling wave). k_to_h0 is
+not reachable: every multigrid solve's assembly writes the bf16 copy itself;
+the transfers' oversized-group branches (more than kRG members, more than kRGS
+list entries) are built by no mesh of the suite.
 """
 import functools
 import os
@@ -90,7 +97,8 @@ import scipy.sparse as sp
 import amg_ref as R
 import test_gpu_amg_setup as S
 import vcycle_ref as V
-from mofhip import DeviceMesh
+from conftest import load_golden
+from mofhip import DeviceMesh, synth
 from mofhip.mesh import (amg_levels, amg_readback, amg_vcycle, amg_vcycle_tables, assembly_readback, force_index32,
                          vcycle_launches)
 
@@ -114,6 +122,12 @@ CASES = {
     "flat7": ("flat7", 3, (0, 2), None, None, ("subcycle",)),
     # the 32-bit index tables forced (mof_test_force_index32): the mirrored, unpacked instances on a regular mesh
     "G1_ico642_index32": ("G1_ico642", 5, (0, 3, 4), None, 0, ("res0_ns", "restrict2", "prolong0_x1", "post0_x1_zh")),
+    # full system groups beside a group of one: 17 = one 16-system prolongation group + 1 = two 8-system
+    # restriction groups + 1; 9 = one 8-system group + 1 for level 1's prolongation (kNS3) and restriction (kNSR)
+    "G1_ico642_smoothed_b17": ("G1_ico642", 17, (0, 8, 16), "1", None,
+                               ("restrict0_sa2", "prolong0_sa_x1", "subcycle")),
+    "hull_chain_b9": ("hull_chain", 9, (0, 7, 8), None, None,
+                      ("res3", "restrict0_sa3", "prolong3_sa", "post3", "subcycle")),
 }
 INDEX32 = ("G1_ico642_index32",)
 # the instance the second run (forced zh) adds
@@ -151,6 +165,7 @@ def inputs(B, N, rhs, adj, open_surface, smooth_rhs=True):
     rng = np.random.default_rng(20)
     r = np.zeros((B, N, 2), dtype=np.float32)
     kinds = {0: "normal", 1: "zero", 2: "rhs" if B == 3 and smooth_rhs else "normal", 3: "rhs", 4: "impulse"}
+    kinds.update({b: "normal" for b in range(5, B)})
     v = boundary_vertex(adj) if open_surface else N // 3
     assert v is not None
     for b in range(B):
@@ -200,7 +215,14 @@ def run(case):
     systems with and without the taps, a mapped subset, retired neighbours,
     and where the case has one the other z format."""
     name, B, systems, smooth, zh_other, _ = CASES[case]
-    (p, n, t, a), I, tk, lam = S.mesh_and_fields(name, B + 1)
+    if name.startswith("G") and len(load_golden(name)["I"]) < B + 1:
+        # a batch longer than the golden recording (G1_ico642: 16 frames): the golden mesh under the
+        # synthetic meshes' travelling wave
+        g = load_golden(name)
+        p, n, t, a, lam = g["coordinates"], g["normals"], g["triangles"], g["areas"], float(g["lambda_"])
+        I, tk = synth.travelling_wave(p, B + 1), np.arange(float(B + 1))
+    else:
+        (p, n, t, a), I, tk, lam = S.mesh_and_fields(name, B + 1)
     old = os.environ.get("MOF_AMG_SMOOTH")
     if smooth is not None:
         os.environ["MOF_AMG_SMOOTH"] = smooth  # read when the handle's hierarchy is built
