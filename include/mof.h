@@ -957,6 +957,65 @@ int mof_rbf_eval(int32_t device, const double *points, int32_t N, const double *
  * result does not depend on it. */
 int mof_test_rbf_pass(int32_t frames);
 
+/* ---- geodesic distances on the mesh -- pyvista's
+ * surface.geodesic_distance as the reference's error score uses it
+ * (utils/find_singularity_point.py:608-720), for many sources at once -------
+ * The definition:
+ *   graph: the mesh's undirected edges;
+ *   length of an edge (a, b): sqrt((dx dx + dy dy) + dz dz) of the handle's
+ *     coordinates in fp64 without contraction (a MOF_GEOM_F32_POINTS handle's
+ *     points widened to fp64 first);
+ *   d(s, v): the minimum over all edge paths s -> v of the fp64 sum of the
+ *     edge lengths, folded left to right from s; d(s, s) = 0; +inf where no
+ *     path exists;
+ *   with a finite limit every d > limit is reported as +inf and every
+ *     d <= limit is unchanged bit for bit.
+ * This is what Dijkstra's algorithm returns in IEEE arithmetic, and the unique
+ * result of relaxing d[v] = min(d[v], d[u] + w_uv) from +inf in any order until
+ * nothing changes: rounded addition is monotone and never decreases its first
+ * operand for w >= 0, every value ever stored is some path's sum, and the final
+ * state admits no further relaxation. The result therefore depends on no
+ * schedule, tile size, pass size or vertex order of the handle, and compares
+ * bit for bit with scipy.sparse.csgraph.dijkstra on the same lengths.
+ * d(a, b) and d(b, a) may differ in the last bits (the fold runs the other way);
+ * the reference passes the true point first, which is the source here. Parity
+ * with pyvista / VTK itself (its own Dijkstra and its float coordinates) is
+ * unpinned, as for mof_closest_vertices.
+ *
+ * sources (S) and targets (Q) are vertex ids of the caller's order; dist is
+ * (S, Q), or (S, N) in the caller's vertex order when targets is NULL (Q is
+ * then ignored). Sources may repeat and be unsorted: the distinct ones are
+ * relaxed once, 64 per pass (one lane each), and every caller's row is gathered
+ * from its source's. limit may be +inf; limit <= 0 or NaN, S < 1, an id that is
+ * no vertex or a NULL sources / dist give MOF_E_ARG with nothing written. Host
+ * pointers, or with MOF_IO_DEVICE device pointers throughout (the ids are
+ * checked after a copy to the host; stream: hipStream_t or NULL); from host
+ * pointers the (S, Q) or (S, N) result is staged on the device whole. The edge
+ * table (neighbour ids and lengths in the handle's internal order) and the tile
+ * adjacency are built on the handle at the first call. Returns when done. */
+int mof_geodesic(mof_mesh *mesh, const int32_t *sources, int32_t S, const int32_t *targets, int32_t Q, double limit,
+                 uint32_t flags, void *stream, double *dist);
+/* The edges (a[k] < b[k], the caller's ids, ascending by (a, b)) and their
+ * lengths w[k] as mof_geodesic uses them; host pointers; no device work.
+ * *total (always written) = edges. When total > cap nothing else is written
+ * and MOF_E_ARG is returned: call again with cap >= *total. */
+int mof_geodesic_edges(mof_mesh *mesh, int64_t cap, int64_t *total, int32_t *a, int32_t *b, double *w);
+/* Tests only: sources per pass (at most 64) and vertices per workgroup tile
+ * (clamped to [4, 256]) of mof_geodesic, 0 = the library's choice (64 and 32).
+ * The result does not depend on either. */
+int mof_test_geodesic_pass(int32_t sources);
+int mof_test_geodesic_tile(int32_t vertices);
+/* Measurement helpers (bench_geodesic.py), for the last mof_geodesic call of
+ * this process: ms[0..2] = host milliseconds of the edge-table / tile-table
+ * build (0 when they existed), of the relaxation (every pass's kernels and
+ * counter reads) and of the gathers; c[0..7] = passes, tile-kernel launches
+ * (one per round enqueued, 8 per look at the counters), tile executions,
+ * rounds up to and including each pass's first round without a change, 1 if
+ * the edge table was built or uploaded, tiles, vertices per tile, sources per
+ * pass. */
+int mof_geodesic_timing(double *ms);
+int mof_geodesic_counters(int64_t *c);
+
 /* Measurement helper for bench.py: launches the PCG SpMV kernel `reps` times
  * back to back on `batch` systems of the last solve's working set, timed with
  * HIP events on the handle's stream. Returns the mean launch time and the

@@ -765,6 +765,8 @@ int mof_mesh_destroy(mof_mesh *m) {
             m->sline = nullptr;
             mof::wind_destroy(m->wind);
             m->wind = nullptr;
+            mof::geo_destroy(m->geo);
+            m->geo = nullptr;
             if (m->stream) (void)hipStreamDestroy(m->stream);
             m->stream = nullptr;
             delete m;  // DevArray destructors free on the current (guarded) device

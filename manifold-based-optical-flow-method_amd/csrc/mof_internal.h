@@ -268,6 +268,7 @@ class HostStage;      // mof_hostio.h
 struct WaveState;     // mof_wave.hip
 struct StreamState;   // mof_streamline.hip
 struct WindState;     // mof_winding.hip
+struct GeoState;      // mof_geodesic.hip
 
 // Host state of one mesh shared by its handles on several devices
 // (mof_mesh_create builds it once, mof_mesh_clone reuses it): the inputs in
@@ -384,6 +385,9 @@ struct mof_mesh {
     // mof_winding_*: the geometry, the polar-ordered neighbour table and the
     // ring-table / pass workspace, built on first use (mof_winding.hip)
     mof::WindState *wind = nullptr;
+    // mof_geodesic / mof_geodesic_edges: the edge table, the tile adjacency
+    // and the pass workspace, built on first use (mof_geodesic.hip)
+    mof::GeoState *geo = nullptr;
 };
 
 namespace mof {
@@ -444,6 +448,9 @@ void wind_destroy(WindState *st);
 // ids, each ring in search order); an exhausted centre's later rings are empty.
 void wind_bfs(const Pattern &pat, const int32_t *centres, int32_t C, int32_t L, std::vector<int64_t> &off,
               std::vector<int32_t> &vtx);
+
+// mof_geodesic* (mof_geodesic.hip)
+void geo_destroy(GeoState *st);
 
 // Timed SpMV launches: each is charged with the systems it actually
 // processed (a system that converged, or failed, earlier in a chunk of

@@ -21,3 +21,5 @@ from .modes import (velocity_modes, velocity_modes_device, spatiotemporal_modes,
                     modes_project, process_V_k_to_complex, calculate_V_k_from_complex, calculate_percentages)
 from .interp import (interpolation, rbf_epsilon, rbf_matrix, rbf_weights, rbf_eval,  # noqa: F401
                      rbf_eval_device)
+from .geodesic import (geodesic_distances, geodesic_distances_device, geodesic_distance, geodesic_edges,  # noqa: F401
+                       compute_displacement_difference, compute_err_for_all_Vk)

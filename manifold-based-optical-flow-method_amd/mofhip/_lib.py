@@ -72,6 +72,8 @@ EXPORTS = (
     "mof_modes_gram", "mof_modes_project", "mof_test_modes_chunk", "mof_test_modes_pass",
     "mof_dd_test_part", "mof_dd_test_halo", "mof_dd_test_gather", "mof_dd_test_launches",
     "mof_dd_test_pcg_inner", "mof_rbf_eval", "mof_test_rbf_pass",
+    "mof_geodesic", "mof_geodesic_edges", "mof_test_geodesic_pass", "mof_test_geodesic_tile",
+    "mof_geodesic_timing", "mof_geodesic_counters",
 )
 
 
@@ -212,6 +214,12 @@ def lib():
             "mof_test_modes_pass": ([i32], ctypes.c_int),
             "mof_rbf_eval": ([i32, P, i32, P, i32, f64, P, P, i32, u32, P, P, P], ctypes.c_int),
             "mof_test_rbf_pass": ([i32], ctypes.c_int),
+            "mof_geodesic": ([P, P, i32, P, i32, f64, u32, P, P], ctypes.c_int),
+            "mof_geodesic_edges": ([P, i64, P, P, P, P], ctypes.c_int),
+            "mof_test_geodesic_pass": ([i32], ctypes.c_int),
+            "mof_test_geodesic_tile": ([i32], ctypes.c_int),
+            "mof_geodesic_timing": ([P], ctypes.c_int),
+            "mof_geodesic_counters": ([P], ctypes.c_int),
             "mof_singularities": ([i32, P, P, i32, i32, P, i32, f64, u32, P, P, P, P, P],
                                   ctypes.c_int),
             "mof_amg_probe": ([P, P, i32, i32, P, P, P, P], ctypes.c_int),

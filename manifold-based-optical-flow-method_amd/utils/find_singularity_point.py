@@ -3,8 +3,10 @@
 Replaced on the GPU: ``process_V_k`` (find_singularity_point.py:28-69, the
 S3 epilogue on the hot path's output, ``mofhip.epilogue``) and the critical
 point search ``find_singularity_points`` / ``find_singularity_points_for_all_Vk``
-(:140-189, :530-558, ``mofhip.singular``). Every other name (classification,
-error metrics -- out of scope) is taken unchanged from the
+(:140-189, :530-558, ``mofhip.singular``), and the error score
+``compute_displacement_difference`` / ``compute_err_for_all_Vk`` (:608-720,
+``mofhip.geodesic``; ``surface`` is a ``DeviceMesh``). Every other name
+(classification -- out of scope) is taken unchanged from the
 reference's module when that module is reachable through the extended
 ``utils`` package path.
 """
@@ -15,6 +17,7 @@ import os as _os
 
 from mofhip.epilogue import velocity_vectors as _velocity_vectors
 from mofhip import singular as _singular
+from mofhip import geodesic as _geodesic
 
 
 def _load_reference_module():
@@ -35,7 +38,8 @@ def _load_reference_module():
     return None
 
 
-_REPLACED = ("process_V_k", "find_singularity_points", "find_singularity_points_for_all_Vk")
+_REPLACED = ("process_V_k", "find_singularity_points", "find_singularity_points_for_all_Vk",
+             "compute_displacement_difference", "compute_err_for_all_Vk")
 _ref = _load_reference_module()
 if _ref is not None:
     globals().update({k: v for k, v in vars(_ref).items()
@@ -59,3 +63,17 @@ def find_singularity_points_for_all_Vk(V_k_coord, coordinates, triangles, eps):
     """Critical point coordinates per timestep (reference :530-558), all
     timesteps in one GPU launch sequence."""
     return _singular.find_singularity_points_for_all_Vk(V_k_coord, coordinates, triangles, eps)
+
+
+def compute_displacement_difference(threshold, singularity_points, true_singularity_points, surface, i, id):
+    """Geodesic distances between true and detected critical points of one
+    frame and the reference's matching (:608-672); ``surface``: a ``DeviceMesh``."""
+    return _geodesic.compute_displacement_difference(threshold, singularity_points, true_singularity_points,
+                                                     surface, i, id)
+
+
+def compute_err_for_all_Vk(true_singularity_points, singularity_points, threshold, surface, turning_point):
+    """The error score over all frames (:675-720), one distance call for all
+    of them; ``surface``: a ``DeviceMesh``."""
+    return _geodesic.compute_err_for_all_Vk(true_singularity_points, singularity_points, threshold, surface,
+                                            turning_point)
