@@ -494,7 +494,8 @@ int mof_test_assembly_readback(mof_mesh *mesh, int32_t system, float *A32, void 
  *   10 of gent (ints; 3 per gather term)   11 regular (the handle's bf16
  *   iterates and level-0 slab)   12 the handle's row kernels read level 0
  *   symmetrically   13 nc (coarsest dofs)   14 cap (systems of
- *   multigrid storage)   15 the level keeps an int8 sweep copy (Ah).
+ *   multigrid storage)   15 bit 0: the level keeps an int8 sweep copy (Ah);
+ *   bit 1: its fp32 operator is stored packed (diagonal and upper blocks).
  * omegas[0..2) = the fine and the coarse smoother damping.
  * sell_off, sell_col, sell_row, diag_pos (n): the level's SELL-64 layout; a
  * padding position has sell_row >= n, or sell_col == sell_row away from
@@ -516,11 +517,13 @@ int mof_test_amg_levels(mof_mesh *mesh, int32_t level, int32_t *n_levels, int64_
                         int32_t *gptr, int32_t *gent);
 /* Test hook: a plain device-to-host copy, after a stream synchronize, of what
  * the handle's last multigrid setup left for its system `system` on level
- * `level` >= 1: A (12 floats per SELL position: 3 rows padded to 4), the
+ * `level` >= 1: A (12 floats per SELL position: 3 rows padded to 4; a level
+ * that keeps its operator packed -- bit 1 of sizes[15] of mof_test_amg_levels
+ * -- is widened on the host, each lower block its upper twin transposed), the
  * block-Jacobi inverse Dh (4 words per node: bf16 entries 0..7) and Dh22 (one
  * bf16 per node: entry 8), the int8 sweep copy Ah (2 words per position: codes
  * 0..7, offset binary) and Ah22 (2 half-words per position: code 8, then the
- * block's bf16 scale) where sizes[15] of mof_test_amg_levels says so, and on
+ * block's bf16 scale) where bit 0 of sizes[15] of mof_test_amg_levels says so, and on
  * the coarsest level cinv (nc x nc floats, row-major). Any output may be
  * NULL. An error without a built multigrid or for a system >= cap. */
 int mof_test_amg_readback(mof_mesh *mesh, int32_t level, int32_t system, float *A, uint32_t *Dh, uint16_t *Dh22,
@@ -554,7 +557,9 @@ int mof_test_galerkin_launches(int64_t *counts);
  * system the cycle skipped), and for each of the nsys systems listed r1 (N
  * words: level 0's residual, bf16 pairs at the aggregates' member positions),
  * taps ([4][N][2] words; a tap in the bf16 format fills N) and coarse (per
- * level >= 1 its b, x, r, y, [n][4] floats each, r at the member positions).
+ * level >= 1 its b, x, r, y, [n][4] floats each, r at the member positions:
+ * the device keeps 12-byte rows, and the hook adds the fourth word, 0 or, on a
+ * row whose three words still hold the sentinel, the sentinel).
  * meta[0..4) = zh in force, xm (level 0's corrected iterate: 1 bf16 in place,
  * 2 float2), the first level of the fused k_subcycle, row blocks per system.
  * Any output but z may be NULL. On a decomposed part's handle

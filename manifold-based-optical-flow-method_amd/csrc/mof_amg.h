@@ -76,6 +76,11 @@ struct AmgLevel {
     // positions and their upper twins' (the products cover the diagonal and
     // upper blocks and write each lower twin as the transpose, st_pair)
     std::vector<int32_t> low, twin;
+    // ... and each diagonal or upper block's index among them in position
+    // order (-1: a lower block or padding), npk of them: where a level keeps
+    // its fp32 operator packed (AmgDevLevel::packed)
+    std::vector<int32_t> pk;
+    int32_t npk = 0;
     // smoothed prolongator (level 0 with AmgParams::smooth): P rows as blocks
     // (bs x 3 floats each, in Q) with CSR pptr / pcol over the fine nodes, and
     // the restriction lists per coarse node: pairs {fine node, P block}. The
@@ -138,14 +143,21 @@ struct AmgDevLevel {
     int32_t ngrp = 0, nggrp = 0;
     DevArray<float> Q, Qm;
     // per system, capacity AmgDevice::cap
-    DevArray<float> A;           // [B][sell_nb][12] (level >= 1)
+    // the fp32 operator only the next level's product reads (amg_build: not the coarsest level,
+    // not a level whose product runs from the system slab): its diagonal and upper blocks alone,
+    // 9 floats each, at pk[position]; that level's gather lists (gent) then name packed indices,
+    // | kMirT for a lower block (its upper twin, read transposed)
+    bool packed = false;
+    int64_t npk = 0;
+    DevArray<int32_t> pk;
+    DevArray<float> A;           // [B][sell_nb][12], or packed [B][npk][9] (level >= 1)
     DevArray<uint32_t> Dh;       // [B][n][4] 3x3 D^-1 bf16 entries 0..7 (level >= 1)
     DevArray<uint16_t> Dh22;     // [B][n] entry (2,2)
     DevArray<uint32_t> Ah;       // sweep copy (not the coarsest), st_a9: [B][sell_nb][2] int8 codes 0..7
     DevArray<uint16_t> Ah22;     // [B][sell_nb][2] code 8 | bf16 scale
     DevArray<float> slab;        // level 1 of a smoothed level 0: one system slab's A as
                                  // [sell_nb][64][12] (k_galerkin_sys<2> -> <3>)
-    DevArray<float> b, x, r, y;  // [B][n][4] (level >= 1); level 0: x [B][n][2], r bf16 pairs [B][n]
+    DevArray<float> b, x, r, y;  // [B][n][3] (level >= 1: 12-byte rows); level 0: x [B][n][2], r bf16 pairs [B][n]
                                  // r is stored in member order of the next level
 };
 

@@ -30,11 +30,12 @@
 // batched loads); coarse levels keep fp32 3x3 blocks (12 floats, rows padded
 // to 4) for the Galerkin products and int8 copies (9 codes + a bf16 scale,
 // 12 B per block, st_a9) for the sweeps, vectors
-// as float4. All sums run in a fixed order: the cycle is
+// as 12-byte rows of three floats (kV3). All sums run in a fixed order: the cycle is
 // deterministic and independent of B.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "mof_amg.h"
@@ -69,14 +70,22 @@ __device__ __forceinline__ bool retired(const int32_t *sysi, int32_t b) {
     return !sysi[b * kSysStride + SI_ACTIVE] || sysi[b * kSysStride + SI_CONV] >= 0;
 }
 
-// per-node vector: BS = 2 -> float2 (stride 2), BS = 3 -> float4 (stride 4)
+// floats per node of a coarse level's vectors (b, x, r, y at levels >= 1):
+// 12-byte rows at 4-byte alignment, system b's rows from b * n * kV3
+constexpr int kV3 = 3;
+struct F3 {
+    float x, y, z;
+};
+static_assert(sizeof(F3) == kV3 * sizeof(float) && alignof(F3) == alignof(float), "a coarse row is three packed floats");
+
+// per-node vector: BS = 2 -> float2 (stride 2), BS = 3 -> F3 (stride kV3, one 12-byte access)
 template <int BS>
 __device__ __forceinline__ void ldv(const float *v, int64_t node, float (&x)[BS]) {
     if constexpr (BS == 2) {
         const float2 t = reinterpret_cast<const float2 *>(v)[node];
         x[0] = t.x; x[1] = t.y;
     } else {
-        const float4 t = reinterpret_cast<const float4 *>(v)[node];
+        const F3 t = reinterpret_cast<const F3 *>(v)[node];
         x[0] = t.x; x[1] = t.y; x[2] = t.z;
     }
 }
@@ -89,7 +98,7 @@ __device__ __forceinline__ void ldr(const float *r, int64_t b, int64_t n, int64_
         x[0] = bf16_lo(h);
         x[1] = bf16_hi(h);
     } else {
-        ldv<BSF>(r + b * n * 4, q, x);
+        ldv<BSF>(r + b * n * kV3, q, x);
     }
 }
 template <int BS>
@@ -97,7 +106,7 @@ __device__ __forceinline__ void stv(float *v, int64_t node, const float (&x)[BS]
     if constexpr (BS == 2)
         reinterpret_cast<float2 *>(v)[node] = make_float2(x[0], x[1]);
     else
-        reinterpret_cast<float4 *>(v)[node] = make_float4(x[0], x[1], x[2], 0.f);
+        reinterpret_cast<F3 *>(v)[node] = F3{x[0], x[1], x[2]};
 }
 // BS x BS block: BS = 2 -> 4 floats, BS = 3 -> 12 floats (rows padded to 4)
 template <int BS>
@@ -116,6 +125,24 @@ __device__ __forceinline__ void ldm(const float *A, int64_t idx, float (&a)[BS][
 }
 template <int BS>
 constexpr int bstride() { return BS == 2 ? 4 : kB3; }
+// A packed 3x3 block: 9 floats at 4-byte alignment (a level whose fp32
+// operator only the next product reads keeps its diagonal and upper blocks
+// this way, AmgDevLevel::packed)
+constexpr int kB9 = 9;
+struct F9 {
+    float v[kB9];
+};
+__device__ __forceinline__ void ldm9(const float *A, int64_t idx, float (&a)[3][3]) {
+    const F9 t = reinterpret_cast<const F9 *>(A)[idx];
+#pragma unroll
+    for (int k = 0; k < kB9; ++k) a[k / 3][k % 3] = t.v[k];
+}
+__device__ __forceinline__ void st9(float *A, int64_t idx, const float (&a)[3][3]) {
+    F9 t;
+#pragma unroll
+    for (int k = 0; k < kB9; ++k) t.v[k] = a[k / 3][k % 3];
+    reinterpret_cast<F9 *>(A)[idx] = t;
+}
 
 template <int BS>
 __device__ __forceinline__ void matvec(const float (&a)[BS][BS], const float (&x)[BS], float (&y)[BS]) {
@@ -180,45 +207,60 @@ __device__ __forceinline__ void st_h9(uint4 *H, uint16_t *H22, int64_t q, const 
 // uint32 words of Ah and uint16 words of Ah22 per block
 constexpr size_t kAhWords = 2, kAh22Words = 2;
 
-__device__ __forceinline__ void st_a9(uint4 *H, uint16_t *H22, int64_t q, const float (&c)[3][3]) {
-    {
-        float m = 0.f;
+// the scale (bf16 bits) and the 9 codes of block c, row-major
+__device__ __forceinline__ uint32_t quant_a9(const float (&c)[3][3], uint32_t (&u)[9]) {
+    float m = 0.f;
 #pragma unroll
-        for (int r = 0; r < 3; ++r)
+    for (int r = 0; r < 3; ++r)
 #pragma unroll
-            for (int k = 0; k < 3; ++k) m = fmaxf(m, fabsf(c[r][k]));
-        const uint32_t sb = bf16_bits(m / 127.f);
-        const float sc = bf16_lo(sb);
-        uint32_t u[9];
+        for (int k = 0; k < 3; ++k) m = fmaxf(m, fabsf(c[r][k]));
+    const uint32_t sb = bf16_bits(m / 127.f);
+    const float sc = bf16_lo(sb);
 #pragma unroll
-        for (int r = 0; r < 3; ++r)
+    for (int r = 0; r < 3; ++r)
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float v = sc > 0.f ? rintf(c[r][k] / sc) : 0.f;
-                u[3 * r + k] = (uint32_t)(fminf(fmaxf(v, -127.f), 127.f) + 128.f);
-            }
-        reinterpret_cast<uint2 *>(H)[q] =
-            make_uint2(u[0] | (u[1] << 8) | (u[2] << 16) | (u[3] << 24), u[4] | (u[5] << 8) | (u[6] << 16) | (u[7] << 24));
-        reinterpret_cast<uint32_t *>(H22)[q] = u[8] | (sb << 16);
-    }
+        for (int k = 0; k < 3; ++k) {
+            const float v = sc > 0.f ? rintf(c[r][k] / sc) : 0.f;
+            u[3 * r + k] = (uint32_t)(fminf(fmaxf(v, -127.f), 127.f) + 128.f);
+        }
+    return sb;
+}
+// block q's words from its codes; TR: the codes of the transposed block
+template <bool TR>
+__device__ __forceinline__ void st_a9(uint4 *H, uint16_t *H22, int64_t q, const uint32_t (&u)[9], uint32_t sb) {
+    auto e = [&](int k) { return TR ? u[3 * (k % 3) + k / 3] : u[k]; };
+    reinterpret_cast<uint2 *>(H)[q] =
+        make_uint2(e(0) | (e(1) << 8) | (e(2) << 16) | (e(3) << 24), e(4) | (e(5) << 8) | (e(6) << 16) | (e(7) << 24));
+    reinterpret_cast<uint32_t *>(H22)[q] = e(8) | (sb << 16);
 }
 // A product's block C at position pos of system b and, for an upper block
 // (tw >= 0: its lower twin's position, AmgLevel::twin), C^T at the twin: the
 // products cover the diagonal and upper blocks only (round 6), and the
-// coarse operator is symmetric to the bit
+// coarse operator is symmetric to the bit. The sweep copy's scale and codes
+// are formed once: the twin's words are the same nine bytes, transposed.
+// pi >= 0: the level keeps its fp32 blocks packed ([c_npk] blocks of 9 floats
+// per system, the diagonal and upper ones alone); C goes to packed index pi
+// and the twin gets no fp32 block.
 __device__ __forceinline__ void st_pair(float *__restrict__ Ac, uint4 *__restrict__ Ah, uint16_t *__restrict__ Ah22,
-                                        int64_t b, int64_t c_sell_nb, int64_t pos, int32_t tw,
-                                        const float (&C)[3][3]) {
-    st3(Ac, b * c_sell_nb + pos, C);
-    if (Ah) st_a9(Ah, Ah22, b * c_sell_nb + pos, C);
+                                        int64_t b, int64_t c_sell_nb, int64_t pos, int32_t tw, int64_t c_npk,
+                                        int32_t pi, const float (&C)[3][3]) {
+    uint32_t u[9] = {}, sb = 0;
+    if (Ah) sb = quant_a9(C, u);
+    if (pi >= 0)
+        st9(Ac, b * c_npk + pi, C);
+    else
+        st3(Ac, b * c_sell_nb + pos, C);
+    if (Ah) st_a9<false>(Ah, Ah22, b * c_sell_nb + pos, u, sb);
     if (tw >= 0) {
-        float T[3][3];
+        if (pi < 0) {
+            float T[3][3];
 #pragma unroll
-        for (int r = 0; r < 3; ++r)
+            for (int r = 0; r < 3; ++r)
 #pragma unroll
-            for (int c = 0; c < 3; ++c) T[r][c] = C[c][r];
-        st3(Ac, b * c_sell_nb + tw, T);
-        if (Ah) st_a9(Ah, Ah22, b * c_sell_nb + tw, T);
+                for (int c = 0; c < 3; ++c) T[r][c] = C[c][r];
+            st3(Ac, b * c_sell_nb + tw, T);
+        }
+        if (Ah) st_a9<true>(Ah, Ah22, b * c_sell_nb + tw, u, sb);
     }
 }
 
@@ -232,10 +274,12 @@ struct GalArgs {
     const int32_t *__restrict__ diag;        // each row's diagonal position
     const uint8_t *__restrict__ dead;        // [nC][3] dofs without a prolongator column
     const int32_t *__restrict__ twin;        // each upper block's lower twin position, or -1
+    const int32_t *__restrict__ pk;          // a packed target: each position's packed index, else null
+    int64_t c_npk;                           // and its packed blocks per system
     const int32_t *__restrict__ gptr;        // [c_sell_nb + 1] each position's range of gather entries
-    const int32_t *__restrict__ gent;        // triples {fine position, P block of i, P block of j}
+    const int32_t *__restrict__ gent;        // triples {fine position or packed index (| kMirT), P block of i, of j}
     const float *__restrict__ Q;             // P blocks
-    float *__restrict__ Ac;                  // [B][c_sell_nb][12]
+    float *__restrict__ Ac;                  // [B][c_sell_nb][12], or packed [B][c_npk][9]
     uint4 *__restrict__ Dh;                  // [B][nC] block-Jacobi D^-1 (st_h9)
     uint16_t *__restrict__ Dh22;
     uint4 *__restrict__ Ah;                  // [B][c_sell_nb] sweep copy (st_a9), or null (the coarsest)
@@ -243,7 +287,8 @@ struct GalArgs {
 };
 
 // where a product reads its fine blocks: level 0's bf16 sweep copy (uint2) or
-// fp32 A (float4) per block, a level >= 1's fp32 A (12 floats per block)
+// fp32 A (float4) per block, a level >= 1's fp32 A (packed, 9 floats per
+// block; the system slab: 12)
 template <int BSF, bool H>
 using GalSrc = std::conditional_t<BSF == 3, float, std::conditional_t<H, uint2, float4>>;
 
@@ -257,14 +302,26 @@ __device__ __forceinline__ void ld_p(const float *__restrict__ Q, int32_t blk, f
 // The fine block of gather entry fp, at A[base + position * stride] (a
 // system's operator: base = b * sell_nb, stride 1; a system slab: base =
 // lane, stride kSlab). A level-0 entry with kMirT is the upper twin, read
-// transposed. fp < 0 is a decomposed part's ghost block: the identity for
+// transposed; so is a packed coarse level's (PK: fp is the packed index of the
+// block or of its upper twin, base = b * npk). fp < 0 is a decomposed part's ghost block: the identity for
 // -1, zero otherwise. Position 0 is read for it and dropped: a branch around
 // the loads costs k_galerkin3_big and k_galerkin_ns<3> registers across an
 // occupancy step (81 and 138 VGPRs; profiles/galerkin_refactor/).
-template <int BSF, typename T>
+template <int BSF, bool PK = false, typename T>
 __device__ __forceinline__ void ld_fine(const T *__restrict__ A, int64_t base, int64_t stride, int32_t fp,
                                         float (&a)[BSF][BSF]) {
-    if constexpr (BSF == 3) {
+    if constexpr (BSF == 3 && PK) {
+        ldm9(A, base + (fp < 0 ? 0 : fp & kMirPos) * stride, a);
+        const bool tr = fp >= 0 && (fp & kMirT);
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = r + 1; c < 3; ++c) {
+                const float up = a[r][c], lo = a[c][r];
+                a[r][c] = tr ? lo : up;
+                a[c][r] = tr ? up : lo;
+            }
+    } else if constexpr (BSF == 3) {
         ldm<3>(A, base + max(fp, 0) * stride, a);
     } else {
         const int64_t q = base + (fp < 0 ? 0 : fp & kMirPos) * stride;
@@ -328,6 +385,7 @@ __device__ __forceinline__ int32_t gal_finish(const GalArgs &g, int32_t b, int64
     // read ahead of the stores: __restrict__ on a member promises the
     // compiler nothing, so it would not move this load above them itself
     const int32_t tw = g.twin[pos];
+    const int32_t pi = g.pk ? g.pk[pos] : -1;
     if (diag) {
 #pragma unroll
         for (int d = 0; d < 3; ++d)
@@ -337,7 +395,7 @@ __device__ __forceinline__ int32_t gal_finish(const GalArgs &g, int32_t b, int64
         inv3(Cm, D);
         st_h9(g.Dh, g.Dh22, (int64_t)b * g.nC + I, D);
     }
-    st_pair(g.Ac, g.Ah, g.Ah22, b, g.c_sell_nb, pos, tw, Cm);
+    st_pair(g.Ac, g.Ah, g.Ah22, b, g.c_sell_nb, pos, tw, g.c_npk, pi, Cm);
     return tw;
 }
 
@@ -374,7 +432,8 @@ __global__ __launch_bounds__(kWG) void k_h0_twins(int64_t nb, const int32_t *__r
 // loaded once and applied to the fine blocks of every system, folded per
 // system in list order. Level 0 (BSF = 2; 7.5x the entries with a smoothed
 // prolongator) reads the smoother's bf16 copy (Afh) or, Afh null, the fp32 A
-// (Af); levels >= 1 (BSF = 3) the fp32 3x3 blocks of Af.
+// (Af); levels >= 1 (BSF = 3) the packed fp32 3x3 blocks of Af (f_sell_nb:
+// the source's blocks per system, packed ones there).
 // Level 0, systems per thread: C3 (512 systems) 6.08 ms per launch at 4, 8.06
 // at 8, 14.7 at 16 (the per-system fine-block gathers, not the shared gather
 // lists, bound it; more systems per thread only lower the occupancy); one
@@ -416,7 +475,7 @@ __global__ __launch_bounds__(kWG) void k_galerkin_ns(GalArgs g, const float *__r
         for (int t = 0; t < NS; ++t) {
             const int64_t base = (int64_t)min(b0 + t, g.B - 1) * f_sell_nb;
             if constexpr (BSF == 3)
-                ld_fine<3>(Af, base, 1, fp, a[t]);
+                ld_fine<3, true>(Af, base, 1, fp, a[t]);
             else if (Afh)
                 ld_fine<2>(Afh, base, 1, fp, a[t]);
             else
@@ -480,7 +539,8 @@ __global__ __launch_bounds__(kWG) void k_galerkin_ent(GalArgs g, int32_t ngrp, c
         ld_p<BSF>(g.Q, ii, qi);
         ld_p<BSF>(g.Q, jj, qj);
 #pragma unroll
-        for (int t = 0; t < kGalENS; ++t) ld_fine<BSF>(Af, (int64_t)min(b0 + t, g.B - 1) * f_sell_nb, 1, fp, a[t]);
+        for (int t = 0; t < kGalENS; ++t)
+            ld_fine<BSF, BSF == 3>(Af, (int64_t)min(b0 + t, g.B - 1) * f_sell_nb, 1, fp, a[t]);
 #pragma unroll
         for (int t = 0; t < kGalENS; ++t) {
             float T[3][3];
@@ -665,7 +725,8 @@ __global__ __launch_bounds__(kWG) void k_galerkin3_big(GalArgs g, int32_t nbig, 
             ld_p<3>(g.Q, ii, qi);
             ld_p<3>(g.Q, jj, qj);
 #pragma unroll
-            for (int t = 0; t < NSB; ++t) ld_fine<3>(Af, (int64_t)min(b0 + t, g.B - 1) * f_sell_nb, 1, fp, a[t]);
+            for (int t = 0; t < NSB; ++t)
+                ld_fine<3, true>(Af, (int64_t)min(b0 + t, g.B - 1) * f_sell_nb, 1, fp, a[t]);
 #pragma unroll
             for (int t = 0; t < NSB; ++t) {
                 float T[3][3];
@@ -795,7 +856,7 @@ struct Lvl {
     const uint16_t *Dh22;                // and entry (2,2)
     const uint4 *Ah;                     // bf16 A for the sweeps: [B][sell_nb] entries 0..7, or null
     const uint16_t *Ah22;                // [B][sell_nb] entry (2,2)
-    float *b, *x, *r, *y;                // [B][n][4] (level 0: x [B][n][2], r bf16 [B][n][2])
+    float *b, *x, *r, *y;                // [B][n][3] (level 0: x [B][n][2], r bf16 [B][n][2])
     const int32_t *agg, *mptr, *apos;    // transition to level + 1
     const int32_t *mlist;                // aggregate members (level 0: r1 gathered in member order)
     const float *Q, *Qm;                 // tentative rows (node order / member order), or P blocks
@@ -873,7 +934,7 @@ __device__ __forceinline__ void spmv_row3(const Lvl &L, int32_t b, int32_t i, co
 
 // coarse level: r = b - A x at the member position of node i
 __device__ __forceinline__ void res3_node(const Lvl &L, int32_t b, int32_t i) {
-    const int64_t vo = (int64_t)b * L.n * 4;
+    const int64_t vo = (int64_t)b * L.n * kV3;
     float ax[3], bi[3];
     spmv_row3(L, b, i, L.x + vo, ax);
     ldv<3>(L.b + vo, i, bi);
@@ -907,7 +968,7 @@ struct SysGroup {
 // and the scaling is a single multiply.
 __device__ __forceinline__ void coarse_store(const Lvl &C, int32_t b, int32_t I, const float (&acc)[3], bool smooth,
                                              float omega) {
-    const int64_t vo = (int64_t)b * C.n * 4;
+    const int64_t vo = (int64_t)b * C.n * kV3;
     stv<3>(C.b + vo, I, acc);
     if (smooth) {
         float d[3][3], x[3];
@@ -923,7 +984,7 @@ __device__ __forceinline__ void coarse_store(const Lvl &C, int32_t b, int32_t I,
 // reads the x0 word of F.x and writes the corrected pair back in that format
 // in place (XM = 1) or as float2 into F.y, full precision for the
 // post-smoothing (XM = 2, see AmgDevice::xm); a coarse level (BSF = 3) keeps
-// float4 rows in F.x.
+// 12-byte rows in F.x.
 template <int BSF>
 __device__ __forceinline__ void ld_xf(const Lvl &F, int32_t b, int32_t i, float (&x)[BSF]) {
     if constexpr (BSF == 2) {
@@ -931,13 +992,13 @@ __device__ __forceinline__ void ld_xf(const Lvl &F, int32_t b, int32_t i, float 
         x[0] = t.x;
         x[1] = t.y;
     } else {
-        ldv<3>(F.x + (int64_t)b * F.n * 4, i, x);
+        ldv<3>(F.x + (int64_t)b * F.n * kV3, i, x);
     }
 }
 template <int BSF, int XM = 0>
 __device__ __forceinline__ void st_xf(const Lvl &F, int32_t b, int32_t i, const float (&x)[BSF]) {
     if constexpr (BSF == 3)
-        stv<3>(F.x + (int64_t)b * F.n * 4, i, x);
+        stv<3>(F.x + (int64_t)b * F.n * kV3, i, x);
     else if constexpr (XM == 2)
         reinterpret_cast<float2 *>(F.y)[(int64_t)b * F.n + i] = make_float2(x[0], x[1]);
     else
@@ -981,7 +1042,7 @@ __device__ __forceinline__ void restrict_node(const Lvl &F, const Lvl &C, int32_
 // coarse level, tentative prolongator: x_i += Q_i y_C[agg(i)]
 __device__ __forceinline__ void prolong_node(const Lvl &F, const Lvl &C, int32_t b, int32_t i) {
     float y[3], xi[3];
-    ldv<3>(C.y + (int64_t)b * C.n * 4, F.agg[i], y);
+    ldv<3>(C.y + (int64_t)b * C.n * kV3, F.agg[i], y);
     ld_xf<3>(F, b, i, xi);
     const float *qi = F.Q + (int64_t)i * 9;
 #pragma unroll
@@ -991,7 +1052,7 @@ __device__ __forceinline__ void prolong_node(const Lvl &F, const Lvl &C, int32_t
 
 // coarse level: y = x + w D^-1 (b - A x)
 __device__ __forceinline__ void post3_node(const Lvl &L, int32_t b, int32_t i, float omega) {
-    const int64_t vo = (int64_t)b * L.n * 4;
+    const int64_t vo = (int64_t)b * L.n * kV3;
     float ax[3], res[3], xi[3], d[3][3], dr[3];
     spmv_row3(L, b, i, L.x + vo, ax);
     ldv<3>(L.b + vo, i, res);
@@ -1102,7 +1163,7 @@ __global__ __launch_bounds__(kWG) void k_restrict(Lvl F, Lvl C, const int32_t *_
 constexpr int kNSR = 8;    // systems per workgroup in the smoothed-P restriction
 constexpr int kNSP = 16;   // systems per thread in the smoothed-P prolongation
 constexpr int kRGS = 512;  // list entries per restriction group (smoothed P)
-// BSF = 3: level 1's smoothed prolongator (AmgParams::smooth1), r as float4
+// BSF = 3: level 1's smoothed prolongator (AmgParams::smooth1), r as 12-byte rows
 // in node order; round 5 (F3): 938 us per 1024-system launch with one
 // (coarse node, system) per thread walking its list
 template <int BSF = 2>
@@ -1190,7 +1251,7 @@ __global__ __launch_bounds__(kWG) void k_restrict0_sa(Lvl F, Lvl C, const int32_
 // P_ik y_C[pcol k]; NS systems per thread share the row's P blocks and
 // columns, each loaded once. Level 0 (BSF = 2, NS = kNSP; the measurements
 // above kNSR): x0_i read as the x0 word, the sum stored in the XM format
-// (st_xf). Level 1 (BSF = 3, NS = kNS3, AmgParams::smooth1): float4 rows in
+// (st_xf). Level 1 (BSF = 3, NS = kNS3, AmgParams::smooth1): 12-byte rows in
 // place (round 5, F3: 559 us per 1024-system launch with one system per
 // thread).
 constexpr int kNS3 = 8;
@@ -1216,7 +1277,7 @@ __global__ __launch_bounds__(kWG) void k_prolong_sa(Lvl F, Lvl C, int32_t nblk, 
         for (int c = 0; c < BSF * 3; ++c) pm[c] = p[c];
         float y[NS][3];
 #pragma unroll
-        for (int t = 0; t < NS; ++t) ldv<3>(C.y + (int64_t)sg.b(t) * C.n * 4, K, y[t]);
+        for (int t = 0; t < NS; ++t) ldv<3>(C.y + (int64_t)sg.b(t) * C.n * kV3, K, y[t]);
 #pragma unroll
         for (int t = 0; t < NS; ++t)
 #pragma unroll
@@ -1261,7 +1322,7 @@ __global__ __launch_bounds__(kWG) void k_prolong0(Lvl F, Lvl C, int32_t nblk, co
 #pragma unroll
     for (int t = 0; t < kProlS; ++t) {
         ld_xf<2>(F, sg.b(t), i, x[t]);
-        ldv<3>(C.y + (int64_t)sg.b(t) * C.n * 4, ag, y[t]);
+        ldv<3>(C.y + (int64_t)sg.b(t) * C.n * kV3, ag, y[t]);
     }
 #pragma unroll
     for (int t = 0; t < kProlS; ++t) {
@@ -1318,8 +1379,8 @@ __global__ __launch_bounds__(kSubWG) void k_subcycle(SubArgs a) {
         const Lvl &C = a.lv[a.last];
         const int32_t nc = 3 * C.n;
         const float *Mi = a.cinv + (int64_t)b * nc * nc;
-        const float *bb = C.b + (int64_t)b * C.n * 4;
-        for (int32_t q = tid; q < nc; q += kSubWG) bl[q] = bb[4 * (q / 3) + q % 3];
+        const float *bb = C.b + (int64_t)b * C.n * kV3;  // dof q of the level: word q
+        for (int32_t q = tid; q < nc; q += kSubWG) bl[q] = bb[q];
         __syncthreads();
         const int32_t d = tid % kMaxCoarse, hf = tid / kMaxCoarse;
         const int32_t chunk = (nc + kH - 1) / kH;
@@ -1341,7 +1402,7 @@ __global__ __launch_bounds__(kSubWG) void k_subcycle(SubArgs a) {
             float t = part[0][d];
 #pragma unroll
             for (int h = 1; h < kH; ++h) t += part[h][d];
-            C.y[(int64_t)b * C.n * 4 + 4 * (d / 3) + d % 3] = t;
+            C.y[(int64_t)b * C.n * kV3 + d] = t;
         }
         __syncthreads();
     }
@@ -1938,6 +1999,17 @@ bool amg_build(mof_mesh *m) {
                 for (size_t k = 0; k < L.low.size(); ++k) tw[L.twin[k]] = L.low[k];
                 put_i(D.twin, tw);
             }
+            // the fp32 operator packed (diagonal and upper blocks, 9 floats each) where only
+            // the next product reads it: not the coarsest level (k_coarse_inverse), and not
+            // level 1 under a smoothed level 0 when its product runs from the system slab
+            // (amg_ensure's C.slab, k_galerkin_sys), which keeps [sell_nb][12]
+            const bool slab_src = l == 1 && H.levels[0].smoothed && H.levels.size() >= 3 && L.n > kSubNodes;
+            D.packed = l + 1 < H.levels.size() && !slab_src;
+            D.npk = D.packed ? L.npk : 0;
+            if (D.packed) {
+                MOF_REQUIRE((int64_t)L.pk.size() == L.sell_nb(), "the level has no packed index table");
+                put_i(D.pk, L.pk);
+            }
             put_i(D.sell_off, L.sell_off);
             put_i(D.sell_col, L.sell_col);
             put_i(D.sell_row, L.sell_row);
@@ -1951,7 +2023,21 @@ bool amg_build(mof_mesh *m) {
             put_i(D.mlist, L.mlist);
             put_i(D.apos, L.apos);
             put_i(D.gptr, L.gptr);
-            put_i(D.gent, L.gent);
+            if (D.packed) {
+                // the lists name packed blocks: a lower block is its upper twin's, transposed
+                std::vector<int32_t> up((size_t)L.sell_nb(), -1), ge(L.gent);
+                for (size_t k = 0; k < L.low.size(); ++k) up[L.low[k]] = L.twin[k];
+                for (size_t e = 0; e < ge.size(); e += 3) {
+                    const int32_t fp = ge[e];
+                    if (fp < 0) continue;
+                    const int32_t pi = L.pk[fp] >= 0 ? L.pk[fp] : (up[fp] >= 0 ? L.pk[up[fp]] | kMirT : -1);
+                    MOF_REQUIRE(pi >= 0, "a gather entry names a position without a block");
+                    ge[e] = pi;
+                }
+                put_i(D.gent, ge);
+            } else {
+                put_i(D.gent, L.gent);
+            }
             put_f(D.Q, L.Q);
             put_f(D.Qm, L.Qm);
             D.smoothed = L.smoothed;
@@ -2055,7 +2141,7 @@ void amg_ensure(mof_mesh *m, int32_t B) {
             // k_galerkin_sys)
             if (D.smoothed && G.aslab.n == 0) G.aslab.alloc((size_t)4 * kSlab * m->pat.sell_nb());
         } else {
-            D.A.alloc((size_t)kB3 * D.sell_nb * B);
+            D.A.alloc(D.packed ? (size_t)kB9 * D.npk * B : (size_t)kB3 * D.sell_nb * B);
             D.A.zero(s);
             // (a level 1 of the fused tiny levels keeps its product by entry:
             // S1s, 400 nodes, 25050 -> 26450 timesteps/s without the chain)
@@ -2069,10 +2155,10 @@ void amg_ensure(mof_mesh *m, int32_t B) {
             }
             D.Dh.alloc((size_t)4 * n * B);
             D.Dh22.alloc((size_t)n * B);
-            D.b.alloc(4 * n * B);
-            D.x.alloc(4 * n * B);
-            D.r.alloc(4 * n * B);
-            D.y.alloc(4 * n * B);
+            D.b.alloc(kV3 * n * B);
+            D.x.alloc(kV3 * n * B);
+            D.r.alloc(kV3 * n * B);
+            D.y.alloc(kV3 * n * B);
         }
     }
     G.cinv.alloc((size_t)G.nc * G.nc * B);
@@ -2112,6 +2198,8 @@ static GalArgs gal_args(const AmgDevLevel &F, const AmgDevLevel &C, int32_t B) {
     g.diag = C.diag_pos.p;
     g.dead = C.dead.p;
     g.twin = C.twin.p;
+    g.pk = C.packed ? C.pk.p : nullptr;
+    g.c_npk = C.npk;
     g.gptr = F.gptr.p;
     g.gent = F.gent.p;
     g.Q = F.Q.p;
@@ -2196,6 +2284,7 @@ void amg_setup_batch(mof_mesh *m, int32_t B, hipStream_t s) {
     // else per position
     for (size_t l = l_first; l + 1 < L; ++l) {
         AmgDevLevel &F = G.lv[l], &C = G.lv[l + 1];
+        MOF_REQUIRE(l == 0 || F.packed, "a product's coarse source keeps no packed operator");
         const GalArgs g = gal_args(F, C, B);
         const bool ent = ent_fits(F);
         if (l == 0 && ent) {
@@ -2208,17 +2297,17 @@ void amg_setup_batch(mof_mesh *m, int32_t B, hipStream_t s) {
         } else if (ent) {
             if (F.nggrp > 0) {
                 ++g_galerkin_launches[kGal3Ent];
-                k_galerkin_ent<3><<<gal_grid(F.nggrp, kGalENS), kWG, 0, s>>>(g, F.nggrp, F.ggrp.p, F.A.p, F.sell_nb);
+                k_galerkin_ent<3><<<gal_grid(F.nggrp, kGalENS), kWG, 0, s>>>(g, F.nggrp, F.ggrp.p, F.A.p, F.npk);
             }
             if (F.nbig > 0) {
                 ++g_galerkin_launches[kGal3Big];
                 k_galerkin3_big<kGalBigNS><<<gal_grid(F.nbig, kGalBigNS), kWG, 0, s>>>(g, F.nbig, F.gbig.p, F.A.p,
-                                                                                      F.sell_nb);
+                                                                                      F.npk);
             }
         } else {
             ++g_galerkin_launches[kGal3Ns];
             k_galerkin_ns<3, kGal3NS><<<gal_grid((C.sell_nb + kWG - 1) / kWG, kGal3NS), kWG, 0, s>>>(
-                g, F.A.p, F.sell_nb, nullptr);
+                g, F.A.p, F.npk, nullptr);
         }
     }
     AmgDevLevel &Lc = G.lv[L - 1];
@@ -2479,7 +2568,7 @@ int mof_test_amg_levels(mof_mesh *m, int32_t level, int32_t *n_levels, int64_t *
                                    level == 0 && m->sym_reads,
                                    G->nc,
                                    G->cap,
-                                   G->lv[level].Ah.n > 1};
+                                   (G->lv[level].Ah.n > 1 ? 1 : 0) | (G->lv[level].packed ? 2 : 0)};
             std::copy(v, v + 16, sizes);
         }
         auto put = [](auto *dst, const auto &src) {
@@ -2536,7 +2625,25 @@ int mof_test_amg_readback(mof_mesh *m, int32_t level, int32_t system, float *A, 
             MOF_REQUIRE(src.n >= per * (b + 1), "multigrid storage smaller than its capacity");
             MOF_HIP(hipMemcpy(dst, src.p + per * b, per * sizeof(*dst), hipMemcpyDeviceToHost));
         };
-        get(A, D.A, mof::kB3 * nb);
+        if (A && D.packed) {
+            // the packed blocks widened to [sell_nb][12]: each lower block is its upper twin transposed
+            MOF_REQUIRE(G->H && G->H->levels.size() == G->lv.size(), "the handle keeps no host hierarchy");
+            const mof::AmgLevel &HL = G->H->levels[level];
+            const size_t npk = (size_t)D.npk;
+            MOF_REQUIRE(D.A.n >= mof::kB9 * npk * (b + 1), "multigrid storage smaller than its capacity");
+            std::vector<float> pa(mof::kB9 * npk);
+            MOF_HIP(hipMemcpy(pa.data(), D.A.p + mof::kB9 * npk * b, sizeof(float) * pa.size(), hipMemcpyDeviceToHost));
+            std::fill(A, A + mof::kB3 * nb, 0.f);
+            auto blk = [&](size_t pos, int32_t pi, bool tr) {
+                for (int r = 0; r < 3; ++r)
+                    for (int c = 0; c < 3; ++c) A[mof::kB3 * pos + 4 * r + c] = pa[mof::kB9 * pi + (tr ? 3 * c + r : 3 * r + c)];
+            };
+            for (size_t pos = 0; pos < nb; ++pos)
+                if (HL.pk[pos] >= 0) blk(pos, HL.pk[pos], false);
+            for (size_t k = 0; k < HL.low.size(); ++k) blk((size_t)HL.low[k], HL.pk[HL.twin[k]], true);
+        } else {
+            get(A, D.A, mof::kB3 * nb);
+        }
         get(Dh, D.Dh, 4 * n);
         get(Dh22, D.Dh22, n);
         get(Ah, D.Ah, mof::kAhWords * nb);
@@ -2644,7 +2751,7 @@ int mof_test_amg_vcycle(mof_mesh *m, int32_t B, const float *r, const int32_t *s
         if (G.xm == 2) fill(G.lv[0].y.p, 2 * nv);
         for (int32_t l = 1; l < L; ++l) {
             mof::AmgDevLevel &D = G.lv[l];
-            for (mof::DevArray<float> *a : {&D.b, &D.x, &D.r, &D.y}) fill(a->p, (size_t)4 * D.n * B);
+            for (mof::DevArray<float> *a : {&D.b, &D.x, &D.r, &D.y}) fill(a->p, (size_t)mof::kV3 * D.n * B);
         }
         mof::DevArray<int32_t> dmap;
         if (smap) {
@@ -2680,6 +2787,7 @@ int mof_test_amg_vcycle(mof_mesh *m, int32_t B, const float *r, const int32_t *s
         }
         size_t per = 0;
         for (int32_t l = 1; l < L; ++l) per += (size_t)16 * G.lv[l].n;
+        std::vector<float> row;
         for (int32_t k = 0; k < nsys; ++k) {
             const size_t b = (size_t)systems[k];
             if (r1)
@@ -2693,10 +2801,18 @@ int mof_test_amg_vcycle(mof_mesh *m, int32_t B, const float *r, const int32_t *s
             float *o = coarse ? coarse + k * per : nullptr;
             for (int32_t l = 1; l < L && o; ++l) {
                 mof::AmgDevLevel &D = G.lv[l];
-                const size_t n4 = (size_t)4 * D.n;
+                // the stored 12-byte rows, widened to the hook's [n][4]: the fourth word is 0, or
+                // the sentinel on a row that still holds it in all three words
+                const size_t n3 = (size_t)mof::kV3 * D.n;
+                row.resize(n3);
                 for (mof::DevArray<float> *a : {&D.b, &D.x, &D.r, &D.y}) {
-                    MOF_HIP(hipMemcpy(o, a->p + b * n4, sizeof(float) * n4, hipMemcpyDeviceToHost));
-                    o += n4;
+                    MOF_HIP(hipMemcpy(row.data(), a->p + b * n3, sizeof(float) * n3, hipMemcpyDeviceToHost));
+                    for (size_t i = 0; i < (size_t)D.n; ++i, o += 4) {
+                        uint32_t wd[4] = {0u, 0u, 0u, 0u};
+                        std::memcpy(wd, &row[mof::kV3 * i], sizeof(float) * mof::kV3);
+                        if (sentinel && wd[0] == *sentinel && wd[1] == *sentinel && wd[2] == *sentinel) wd[3] = *sentinel;
+                        std::memcpy(o, wd, sizeof(wd));
+                    }
                 }
             }
         }

@@ -569,6 +569,8 @@ void build_amg(const Pattern &fine, const double *e_internal, const AmgParams &p
             if (C.sell_blk[pos] >= 0) cpos[C.sell_blk[pos]] = (int32_t)pos;
         C.low.clear();
         C.twin.clear();
+        C.pk.assign(C.sell_blk.size(), -1);
+        C.npk = 0;
         F.gent.clear();
         F.gent.reserve(by_block.size() / 2 + 3 * (size_t)C.n);
         for (int64_t pos = 0; pos < (int64_t)C.sell_blk.size(); ++pos) {
@@ -582,6 +584,7 @@ void build_amg(const Pattern &fine, const double *e_internal, const AmgParams &p
                     C.low.push_back((int32_t)pos);
                     C.twin.push_back(cpos[q]);
                 } else {
+                    C.pk[pos] = C.npk++;
                     F.gent.insert(F.gent.end(), by_block.begin() + 3 * (size_t)cnt[p],
                                   by_block.begin() + 3 * (size_t)cnt[p + 1]);
                 }

@@ -478,7 +478,8 @@ def amg_levels(mesh: "DeviceMesh", device=None) -> dict:
     """Tests only (mof_test_amg_levels): the host multigrid hierarchy the
     handle's preconditioner was built from (after a multigrid solve), as
     ``{"regular", "omega", "omega1", "nc", "cap", "levels": [...]}``; each level
-    a dict of ``n, bs, sell_nb, smoothed, sym, has_Ah`` and the arrays
+    a dict of ``n, bs, sell_nb, smoothed, sym, has_Ah, packed`` (the device keeps
+    the level's fp32 operator packed: diagonal and upper blocks, 9 floats each) and the arrays
     ``sell_off, sell_col, sell_row, diag_pos``, level 0 ``mirror``, levels >= 1
     ``dead`` (n, 3) and ``twin``, and for the transition to the next level
     ``agg, pptr, pcol, Q`` (P blocks, bs, 3), ``gptr, gent`` (terms, 3)."""
@@ -496,7 +497,7 @@ def amg_levels(mesh: "DeviceMesh", device=None) -> dict:
             n, bs, nb = int(sz[0]), int(sz[1]), int(sz[2])
             i32 = lambda k: np.zeros(int(k), dtype=np.int32)  # noqa: E731
             lv = {"n": n, "bs": bs, "sell_nb": nb, "smoothed": bool(sz[4]), "sym": bool(sz[12]),
-                  "has_Ah": bool(sz[15]), "sell_off": i32(sz[3]), "sell_col": i32(nb), "sell_row": i32(nb),
+                  "has_Ah": bool(sz[15] & 1), "packed": bool(sz[15] & 2), "sell_off": i32(sz[3]), "sell_col": i32(nb), "sell_row": i32(nb),
                   "diag_pos": i32(n), "dead": np.zeros((n, 3) if l else (0, 3), dtype=np.uint8),
                   "twin": i32(nb if l else 0), "mirror": i32(0 if l else nb), "agg": i32(sz[5]), "pptr": i32(sz[6]),
                   "pcol": i32(sz[7]), "Q": np.zeros((int(sz[8]) // (3 * bs), bs, 3), dtype=np.float32),
@@ -515,7 +516,8 @@ def amg_readback(mesh: "DeviceMesh", level: int, system: int, n: int, sell_nb: i
                  device=None) -> dict:
     """Tests only (mof_test_amg_readback): what the handle's last multigrid
     setup left for ``system`` on coarse level ``level`` (its ``n``, ``sell_nb``
-    and ``has_Ah`` from ``amg_levels``): ``A`` (sell_nb, 3, 4) float32, ``Dh``
+    and ``has_Ah`` from ``amg_levels``): ``A`` (sell_nb, 3, 4) float32 (a packed
+    level's blocks widened on the host, each lower block its upper twin transposed), ``Dh``
     (n, 4) uint32 and ``Dh22`` (n,) uint16, with ``has_Ah`` the sweep copy ``Ah``
     (sell_nb, 2) uint32 and ``Ah22`` (sell_nb, 2) uint16, and with ``nc`` > 0 (the
     coarsest level) ``cinv`` (nc, nc) float32."""
@@ -593,7 +595,8 @@ def amg_vcycle(mesh: "DeviceMesh", r, level_sizes, systems=(), smap=None, retire
     the pre-sweep, after the prolongation, after the post-sweep: (N,) uint32
     in the bf16 pair format, the last two (N, 2) float32 words with xm = 2;
     empty without ``tap``) and ``coarse``: per level >= 1 a dict of ``b, x, r,
-    y`` (n, 4) float32."""
+    y`` (n, 4) float32: the device's 12-byte rows and a fourth word, 0 or, on a
+    row that still holds the sentinel, the sentinel."""
     r = np.ascontiguousarray(r, dtype=np.float32)
     B, N = r.shape[0], r.shape[1]
     assert r.shape == (B, N, 2)
