@@ -447,12 +447,7 @@ int mof_io_guard(const std::function<void()> &f) { return guarded(f); }
 namespace mof {
 
 std::atomic<int> g_force_index32{0};
-std::atomic<int> g_force_residual_rows{0};
-std::atomic<int> g_force_residual_trips{0};
-std::atomic<int64_t> g_residual_launches[3];
-std::atomic<int> g_force_assembly_rows{0};
-std::atomic<int> g_force_assembly_trips{0};
-std::atomic<int64_t> g_assembly_launches[3];
+StagedHooks g_staged_res, g_staged_asm;
 
 void raise_lds_limit(LdsLimit &st, int device, std::initializer_list<const void *> kernels, int64_t cap) {
     MOF_REQUIRE(device >= 0 && device < LdsLimit::kMaxDev, "device index out of range");
@@ -495,10 +490,11 @@ void mesh_set_own(mof_mesh *m, int32_t nown) {
         m->sell_idx.alloc(mt->packed.size());
         m->sell_idx.upload(mt->packed.data(), mt->packed.size(), m->stream);
     }
-    m->res_lds_bytes = res_staged_bytes(m->pat);
-    m->res_lds = m->res_lds_bytes <= kResLdsCap && !g_force_residual_rows.load();
-    m->asm_lds_bytes = asm_staged_bytes(m->pat);
-    m->asm_lds = asm_staged_fits(m->pat) && !g_force_assembly_rows.load();
+    auto staged = [&](const StagedKind &k, const StagedHooks &h) {
+        return StagedState{staged_bytes(m->pat, k), staged_fits(m->pat, k) && !h.force_rows.load()};
+    };
+    m->res_lds = staged(kStagedRes, g_staged_res);
+    m->asm_lds = staged(kStagedAsm, g_staged_asm);
     int64_t own = 0;  // positions read at their own place: diagonal + upper blocks
     for (int32_t v : mir) own += v >= 0 && !(v & kMirT);
     m->blocks_read = own;
@@ -1255,16 +1251,39 @@ int mof_amg_probe(const int32_t *tri, const double *e, int32_t N, int32_t M, int
     });
 }
 
+// The probes' mesh: the internal order and pattern of mof_mesh_create (host
+// half only; coordinates play no part in either).
+static void probe_host_mesh(mof_mesh &m, const int32_t *tri, int32_t N, int32_t M, uint32_t flags) {
+    const std::vector<double> zero(3 * (size_t)std::max(N, M), 0.0);
+    mof::mesh_prepare_host(&m, zero.data(), zero.data(), tri, zero.data(), N, M, flags, nullptr, nullptr);
+}
+
+// One staged kind's probe, hook switch and launch counters (mof_internal.h).
+static int staged_probe(const mof::StagedKind &k, const int32_t *tri, int32_t N, int32_t M, uint32_t flags,
+                        int64_t *staged_bytes, int32_t *staged_used) {
+    return guarded([&] {
+        MOF_REQUIRE(tri && staged_bytes && N > 0 && M > 0, "bad arguments");
+        mof_mesh m;
+        probe_host_mesh(m, tri, N, M, flags);
+        *staged_bytes = mof::staged_bytes(m.pat, k);
+        if (staged_used) *staged_used = mof::staged_fits(m.pat, k);
+    });
+}
+static int staged_hook(std::atomic<int> &hook, int32_t on) { return guarded([&] { hook.store(on != 0); }); }
+static int staged_launches(const mof::StagedHooks &h, int64_t *counts) {
+    return guarded([&] {
+        MOF_REQUIRE(counts, "NULL argument");
+        for (int k = 0; k < 3; ++k) counts[k] = h.launches[k].load();
+    });
+}
+
 int mof_index_probe(const int32_t *tri, int32_t N, int32_t M, uint32_t flags, int32_t sym, int64_t *sell_nb,
                     int32_t *sell_off, int32_t *col, int32_t *mir, uint32_t *packed, int32_t *sym_used,
                     int32_t *packed_used) {
     return guarded([&] {
         MOF_REQUIRE(tri && sell_nb && N > 0 && M > 0, "bad arguments");
-        // the internal order and pattern of mof_mesh_create (host half only;
-        // coordinates play no part in either)
         mof_mesh m;
-        const std::vector<double> zero(3 * (size_t)std::max(N, M), 0.0);
-        mof::mesh_prepare_host(&m, zero.data(), zero.data(), tri, zero.data(), N, M, flags, nullptr, nullptr);
+        probe_host_mesh(m, tri, N, M, flags);
         const mof::Pattern &P = m.pat;
         bool used = false;
         const std::vector<int32_t> table = mof::sell_mirror(P, N, sym < 0 ? -1 : (sym != 0), &used);
@@ -1288,57 +1307,19 @@ int mof_test_force_index32(int32_t on) {
 
 int mof_residual_probe(const int32_t *tri, int32_t N, int32_t M, uint32_t flags, int64_t *staged_bytes,
                        int32_t *staged_used) {
-    return guarded([&] {
-        MOF_REQUIRE(tri && staged_bytes && N > 0 && M > 0, "bad arguments");
-        mof_mesh m;  // the internal order and pattern of mof_mesh_create (host half only)
-        const std::vector<double> zero(3 * (size_t)std::max(N, M), 0.0);
-        mof::mesh_prepare_host(&m, zero.data(), zero.data(), tri, zero.data(), N, M, flags, nullptr, nullptr);
-        *staged_bytes = mof::res_staged_bytes(m.pat);
-        if (staged_used) *staged_used = *staged_bytes <= mof::kResLdsCap;
-    });
+    return staged_probe(mof::kStagedRes, tri, N, M, flags, staged_bytes, staged_used);
 }
-
-int mof_test_force_residual_rows(int32_t on) {
-    return guarded([&] { mof::g_force_residual_rows.store(on != 0); });
-}
-
-int mof_test_force_residual_trips(int32_t on) {
-    return guarded([&] { mof::g_force_residual_trips.store(on != 0); });
-}
-
-int mof_test_residual_launches(int64_t *counts) {
-    return guarded([&] {
-        MOF_REQUIRE(counts, "NULL argument");
-        for (int k = 0; k < 3; ++k) counts[k] = mof::g_residual_launches[k].load();
-    });
-}
+int mof_test_force_residual_rows(int32_t on) { return staged_hook(mof::g_staged_res.force_rows, on); }
+int mof_test_force_residual_trips(int32_t on) { return staged_hook(mof::g_staged_res.force_trips, on); }
+int mof_test_residual_launches(int64_t *counts) { return staged_launches(mof::g_staged_res, counts); }
 
 int mof_assembly_probe(const int32_t *tri, int32_t N, int32_t M, uint32_t flags, int64_t *staged_bytes,
                        int32_t *staged_used) {
-    return guarded([&] {
-        MOF_REQUIRE(tri && staged_bytes && N > 0 && M > 0, "bad arguments");
-        mof_mesh m;  // the internal order and pattern of mof_mesh_create (host half only)
-        const std::vector<double> zero(3 * (size_t)std::max(N, M), 0.0);
-        mof::mesh_prepare_host(&m, zero.data(), zero.data(), tri, zero.data(), N, M, flags, nullptr, nullptr);
-        *staged_bytes = mof::asm_staged_bytes(m.pat);
-        if (staged_used) *staged_used = mof::asm_staged_fits(m.pat);
-    });
+    return staged_probe(mof::kStagedAsm, tri, N, M, flags, staged_bytes, staged_used);
 }
-
-int mof_test_force_assembly_rows(int32_t on) {
-    return guarded([&] { mof::g_force_assembly_rows.store(on != 0); });
-}
-
-int mof_test_force_assembly_trips(int32_t on) {
-    return guarded([&] { mof::g_force_assembly_trips.store(on != 0); });
-}
-
-int mof_test_assembly_launches(int64_t *counts) {
-    return guarded([&] {
-        MOF_REQUIRE(counts, "NULL argument");
-        for (int k = 0; k < 3; ++k) counts[k] = mof::g_assembly_launches[k].load();
-    });
-}
+int mof_test_force_assembly_rows(int32_t on) { return staged_hook(mof::g_staged_asm.force_rows, on); }
+int mof_test_force_assembly_trips(int32_t on) { return staged_hook(mof::g_staged_asm.force_trips, on); }
+int mof_test_assembly_launches(int64_t *counts) { return staged_launches(mof::g_staged_asm, counts); }
 
 int mof_test_assembly_readback(mof_mesh *m, int32_t system, float *A32, void *A0h, double *rhs, int32_t *have_A0h) {
     return guarded([&] {

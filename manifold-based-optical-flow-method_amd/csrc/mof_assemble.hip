@@ -12,6 +12,7 @@
 #include "mof_amg.h"
 #include "mof_internal.h"
 #include "mof_rowkern.h"
+#include "mof_staged.h"
 
 namespace mof {
 namespace {
@@ -439,14 +440,40 @@ __global__ __launch_bounds__(kWG) void k_assemble_mixed(
     *reinterpret_cast<double2 *>(rhs + 2 * vi) = make_double2(f0, f1);
 }
 
+// The row assembly's argument block (k_assemble_rows_rc, k_assemble_lds): the fp32
+// operator's tables with the batch's I rows in the internal order (op.u = null,
+// op.I0 = J0, op.ldI = N), then what only the assembly reads and its outputs.
+struct AsmArgs {
+    OpArgs<float> op;
+    int32_t B;
+    int64_t sell_nb;
+    const int32_t *vptr, *tslot;  // tslot: an incidence's two other corners' slots of the row
+    const int32_t *mir;           // symmetric layout: the mirror table, else null
+    int32_t nown;                 // rows and columns past it are a decomposed part's ghosts
+    int block_jacobi;
+    const double *area, *J1, *dt;  // J1: the I rows of the next timestep, like op.I0
+    float *A, *dinv32;
+    double *rhs;
+    uint2 *Ah;  // multigrid: the level-0 smoother's bf16 operator, else null
+};
+AsmArgs asm_args(mof_mesh *m, int32_t B, const double *J0, const double *J1, bool block_jacobi, uint2 *Ah) {
+    Workspace &w = m->ws;
+    AsmArgs a{make_op<float>(m, m->a2s32.p, m->w12_32.p, nullptr), B, m->pat.sell_nb(), m->vptr.p, m->tslot.p,
+              m->sym_reads ? m->sell_mir.p : nullptr, m->n_own, block_jacobi ? 1 : 0, m->area.p, J1, w.dt.p,
+              w.A32.p, w.dinv32.p, w.rhs.p, Ah};
+    a.op.I0 = J0;
+    return a;
+}
+
 // One stored slot of row i of one system: the fp32 block (+ lambda a2), its
 // bf16 copy (the identity on a decomposed part's ghost rows and columns) and,
 // with the diagonal block, its inverse and f_i. Shared by the row and the
 // staged kernel.
 __device__ __forceinline__ void row_slot_store(const float (&acc)[4], float4 s4, bool diag, bool ghost, int64_t qq,
-                                               int64_t vi, double f0, double f1, int block_jacobi,
-                                               float *__restrict__ A, float *__restrict__ dinv32,
-                                               double *__restrict__ rhs, uint2 *__restrict__ Ah) {
+                                               int64_t vi, double f0, double f1, const AsmArgs &a) {
+    float *__restrict__ A = a.A, *__restrict__ dinv32 = a.dinv32;
+    double *__restrict__ rhs = a.rhs;
+    uint2 *__restrict__ Ah = a.Ah;
     const float Av[4] = {acc[0] + s4.x, acc[1] + s4.y, acc[2] + s4.z, acc[3] + s4.w};
     reinterpret_cast<float4 *>(A)[qq] = make_float4(Av[0], Av[1], Av[2], Av[3]);
     if (Ah) {
@@ -463,7 +490,7 @@ __device__ __forceinline__ void row_slot_store(const float (&acc)[4], float4 s4,
     if (!diag) return;
     double inv[4];
     const double d0 = Av[0], d1 = Av[1], d2 = Av[2], d3 = Av[3];
-    if (block_jacobi) {
+    if (a.block_jacobi) {
         const double det = d0 * d3 - d1 * d2;
         inv[0] = d3 / det; inv[1] = -d1 / det; inv[2] = -d2 / det; inv[3] = d0 / det;
     } else {
@@ -479,11 +506,8 @@ __device__ __forceinline__ void row_slot_store(const float (&acc)[4], float4 s4,
 // the diagonal block's inverse and f_i.
 template <int WMAX>
 __device__ __forceinline__ void rows_store(const float (&acc)[WMAX][4], double f0, double f1, int32_t i, int32_t b,
-                                           int32_t N, int32_t deg, int64_t o, int64_t sell_nb,
-                                           const int32_t *__restrict__ sell_col, const float *__restrict__ a2s,
-                                           int block_jacobi, float *__restrict__ A, float *__restrict__ dinv32,
-                                           double *__restrict__ rhs, uint2 *__restrict__ Ah, int32_t nown,
-                                           const int32_t *__restrict__ mir) {
+                                           int32_t deg, int64_t o, const AsmArgs &a) {
+    const int32_t *__restrict__ mir = a.mir;
 #pragma unroll
     for (int z = 0; z < WMAX; ++z) {
         if (z >= deg) continue;
@@ -491,9 +515,9 @@ __device__ __forceinline__ void rows_store(const float (&acc)[WMAX][4], double f
         // symmetric layout: lower blocks are read as transposed upper
         // ones and never leave the registers
         if (mir && (mir[pos] & kMirT)) continue;
-        const bool g = Ah && (i >= nown || sell_col[pos] >= nown);
-        row_slot_store(acc[z], reinterpret_cast<const float4 *>(a2s)[pos], z == 0, g, (int64_t)b * sell_nb + pos,
-                       (int64_t)b * N + i, f0, f1, block_jacobi, A, dinv32, rhs, Ah);
+        const bool g = a.Ah && (i >= a.nown || a.op.sell_col[pos] >= a.nown);
+        row_slot_store(acc[z], reinterpret_cast<const float4 *>(a.op.a2s)[pos], z == 0, g,
+                       (int64_t)b * a.sell_nb + pos, (int64_t)b * a.op.N + i, f0, f1, a);
     }
 }
 
@@ -514,9 +538,6 @@ __device__ __forceinline__ void rows_store(const float (&acc)[WMAX][4], double f
 // per 512-system launch at C3), 2 / 4 systems per thread sharing each
 // triangle's geometry (VGPRs 124 -> 290, 10.0 / 10.4 / 14.6 ms at 1 / 2 / 4),
 // a mul-add fold (11.9 ms), LDS slot accumulators (21.0 ms).
-struct TriGeo {
-    const double *gw, *e, *area, *J0, *J1, *dt;  // J0 / J1: the batch's I rows (internal order, stride N)
-};
 // Round 4: the a1 fold in ambient 3-D. a1's block (i, j) is
 // sum_T w_ij (E_i gI_T)(E_j gI_T)^T = E_i G_ij E_j^T with the symmetric 3x3
 // G_ij = sum_T w_ij gI_T gI_T^T (compute_a1 :273-285), so a row folds one
@@ -613,15 +634,13 @@ __device__ __forceinline__ void asm_inc_term(int32_t i, bool real, int32_t c, in
 // (profiles/r04_ab/asm_pre/)
 template <int WMAX>
 __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(WMAX <= 8 ? 4 : 1))) void k_assemble_rows_rc(
-    int32_t N, int32_t M, int32_t nblk, int32_t B, int64_t sell_nb, const int32_t *__restrict__ sell_off,
-    const int32_t *__restrict__ sell_col, const int32_t *__restrict__ vptr, const int32_t *__restrict__ tsell_off,
-    const int4 *__restrict__ tinc, const int32_t *__restrict__ tslot, const float *__restrict__ w12,
-    const float *__restrict__ a2s, int block_jacobi, float *__restrict__ A, float *__restrict__ dinv32,
-    double *__restrict__ rhs, uint2 *__restrict__ Ah, int32_t nown, const int32_t *__restrict__ mir, TriGeo geo) {
+    AsmArgs a, int32_t nblk) {
+    const OpArgs<float> &op = a.op;
+    const int32_t N = op.N, M = op.M;
     int32_t rb, b;
-    if (!xcd_map(nblk, B, rb, b, kGrpAsm)) return;
-    const double *I0b = geo.J0 + (int64_t)b * N, *I1b = geo.J1 + (int64_t)b * N;
-    const double hb = geo.dt[b];
+    if (!xcd_map(nblk, a.B, rb, b, kGrpAsm)) return;
+    const double *I0b = op.I0 + (int64_t)b * N, *I1b = a.J1 + (int64_t)b * N;
+    const double hb = a.dt[b];
 #pragma unroll 1
     for (int r = 0; r < kRows; ++r) {
         const int32_t i = rb * kRowsPerWG + r * kWG + threadIdx.x;
@@ -631,32 +650,32 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(WMAX <= 8 ?
         float G[WMAX][6];  // the slots' 3x3 a1 sums (symmetric: xx xy xz yy yz zz)
         double ei[6];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) ei[k] = geo.e[6 * (int64_t)i + k];
+        for (int k = 0; k < 6; ++k) ei[k] = op.e[6 * (int64_t)i + k];
 #pragma unroll
         for (int z = 0; z < WMAX; ++z)
 #pragma unroll
             for (int x = 0; x < 6; ++x) G[z][x] = 0.f;
         double f0 = 0.0, f1 = 0.0;
         const double Ii0 = I0b[i], pdi = (I1b[i] - Ii0) / hb;
-        const int32_t to = tsell_off[s], tw = (tsell_off[s + 1] - to) >> 6;
+        const int32_t to = op.tsell_off[s], tw = (op.tsell_off[s + 1] - to) >> 6;
         for (int32_t t = 0; t < tw; ++t) {
             const int64_t e = (int64_t)to + (int64_t)t * kSlice + l;
-            const int4 q = tinc[e];
-            const int32_t sl = tslot[e];
+            const int4 q = op.tinc[e];
+            const int32_t sl = a.tslot[e];
             const int64_t T = min(q.x, M - 1);  // padding (T = M): weight 0, no f term
             double g[9];
 #pragma unroll
-            for (int k = 0; k < 9; ++k) g[k] = geo.gw[9 * T + k];
-            const double At = geo.area[T];
-            const float wv = w12[q.x];
+            for (int k = 0; k < 9; ++k) g[k] = op.gw[9 * T + k];
+            const double At = a.area[T];
+            const float wv = op.w12[q.x];
             const int32_t vj = q.z, vk = q.w;
             const double aj = I0b[vj], ak = I0b[vk];
             asm_inc_term<WMAX>(i, q.x < M, q.y, vj, vk, sl, g, At, wv, ei, Ii0, pdi, aj, ak, I1b[vj], I1b[vk], hb, f0,
                                f1, G);
         }
-        g3_project<WMAX>(G, ei, vptr[i + 1] - vptr[i], sell_off[s] + l, sell_col, geo.e, mir, acc);
-        rows_store<WMAX>(acc, f0, f1, i, b, N, vptr[i + 1] - vptr[i], sell_off[s] + l, sell_nb, sell_col, a2s,
-                         block_jacobi, A, dinv32, rhs, Ah, nown, mir);
+        const int32_t deg = a.vptr[i + 1] - a.vptr[i];
+        g3_project<WMAX>(G, ei, deg, op.sell_off[s] + l, op.sell_col, op.e, a.mir, acc);
+        rows_store<WMAX>(acc, f0, f1, i, b, deg, op.sell_off[s] + l, a);
     }
 }
 
@@ -675,10 +694,12 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(WMAX <= 8 ?
 // slots in the row kernel's order, so A32, A0h, dinv32 and rhs keep their bits.
 //
 // Staged planes of a slice of wt incidence slots and wa a2 slots
-// (asm_slice_bytes, mof_internal.h): E 3 planes; INC 7 wt {tinc | g0 g1 |
+// (kStagedAsm, mof_internal.h): E 3 planes; INC 7 wt {tinc | g0 g1 |
 // g2 g3 | g4 g5 | g6 g7 | g8 A_T | w12 tslot - -}; SLT 3 wa {flags e_j[0..2] |
 // e_j[3..5] - | lambda a2}. Flags: 1 = stored (a block of the row, not a
 // transposed lower one), 2 = ghost row or column (its bf16 copy is the identity).
+// E and an incidence slot's first six planes are the ones the staged residual
+// has too (stage_e, stage_inc_geo, mof_staged.h).
 //
 // 8 waves x 8 trips (C3, 1536 systems, per launch; profiles/asm_lds/
 // ab_levers.jsonl): 16 waves at 2 / 4 / 8 trips 17.06 / 16.09 / 15.30 ms, 8
@@ -706,71 +727,56 @@ constexpr int32_t kGrpAsmLds = 1;      // an XCD walks consecutive slices of one
 // with the row kernel
 constexpr int64_t kAsmLdsFill = MOF_ASM_LDS_FILL;
 template <int W, int TRIPS>
-__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))) void k_assemble_lds(
-    int32_t N, int32_t M, int32_t nsl, int32_t B, int64_t sell_nb, const int32_t *__restrict__ sell_off,
-    const int32_t *__restrict__ sell_col, const int32_t *__restrict__ vptr, const int32_t *__restrict__ tsell_off,
-    const int4 *__restrict__ tinc, const int32_t *__restrict__ tslot, const float *__restrict__ w12,
-    const float *__restrict__ a2s, int block_jacobi, float *__restrict__ A, float *__restrict__ dinv32,
-    double *__restrict__ rhs, uint2 *__restrict__ Ah, int32_t nown, const int32_t *__restrict__ mir, TriGeo geo) {
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))) void k_assemble_lds(AsmArgs a,
+                                                                                               int32_t nsl) {
     extern __shared__ double2 asm_lds[];
-    constexpr int NT = 64 * W, PW = W * TRIPS, WMAX = kAsmLdsMaxW;
+    constexpr int NT = 64 * W, PW = W * TRIPS, WMAX = kStagedAsm.max_w;
+    const OpArgs<float> &op = a.op;
+    const int32_t N = op.N, M = op.M, B = a.B;
     int32_t s, chunk;
     if (!xcd_map(nsl, (B + PW - 1) / PW, s, chunk, kGrpAsmLds)) return;  // workgroup-uniform
     // the wave's number as a scalar: its system, I rows and dt stay in SGPRs
     const int32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), l = threadIdx.x & 63;
-    const int32_t o = sell_off[s], wa = (sell_off[s + 1] - o) >> 6;
-    const int32_t to = tsell_off[s], wt = (tsell_off[s + 1] - to) >> 6;
+    const auto [o, wa, to, wt] = slice_view(op.sell_off, op.tsell_off, s);
     double2 *const E = asm_lds, *const INC = asm_lds + 3 * 64, *const SLT = INC + 7 * 64 * wt;
     // ---- staging (all NT threads; lanes past N - 1 of the last slice stage
     // the padding the tables hold for them, row N - 1's bases and no stored slot)
-    for (int32_t q = threadIdx.x; q < 3 * 64; q += NT) {
-        const int32_t k = q >> 6, ll = q & 63;
-        E[q] = *reinterpret_cast<const double2 *>(geo.e + 6 * (int64_t)min(64 * s + ll, N - 1) + 2 * k);
-    }
+    stage_e<NT>(E, op.e, s, N);
     for (int32_t q = threadIdx.x; q < wt * 2 * 64; q += NT) {
         const int32_t ll = q & 63, part = (q >> 6) & 1, t = q >> 7;
         const int64_t e = (int64_t)to + t * 64 + ll;
-        const int4 r = tinc[e];
-        const int64_t T = min(r.x, M - 1);  // padding (T = M): weight w12[M] = 0, no f term
-        const double *g = geo.gw + 9 * T;
-        double2 *P = INC + (7 * t) * 64 + ll;
-        if (part == 0) {
-            *reinterpret_cast<int4 *>(P) = r;
-            P[1 * 64] = make_double2(g[0], g[1]);
-            P[2 * 64] = make_double2(g[2], g[3]);
-            P[3 * 64] = make_double2(g[4], g[5]);
-        } else {
-            P[4 * 64] = make_double2(g[6], g[7]);
-            P[5 * 64] = make_double2(g[8], geo.area[T]);
-            *reinterpret_cast<int4 *>(P + 6 * 64) = make_int4(__float_as_int(w12[r.x]), tslot[e], 0, 0);
-        }
+        const int4 r = op.tinc[e];
+        // padding (T = M): weight w12[M] = 0, no f term
+        double2 *P = stage_inc_geo<7>(INC, t, ll, part, r, op.gw, M, a.area, min(r.x, M - 1));
+        if (part == 1)
+            *reinterpret_cast<int4 *>(P + 6 * 64) = make_int4(__float_as_int(op.w12[r.x]), a.tslot[e], 0, 0);
     }
     for (int32_t q = threadIdx.x; q < wa * 64; q += NT) {
         const int32_t z = q >> 6, ll = q & 63, i = 64 * s + ll;
         const int64_t pos = (int64_t)o + q;
-        const int32_t j = sell_col[pos];
-        const int32_t deg = i < N ? vptr[i + 1] - vptr[i] : 0;
+        const int32_t j = op.sell_col[pos];
+        const int32_t deg = i < N ? a.vptr[i + 1] - a.vptr[i] : 0;
         int32_t fl = 0;
-        if (z < deg && !(mir && (mir[pos] & kMirT))) fl |= 1;
-        if (i >= nown || j >= nown) fl |= 2;
-        const double *ej = geo.e + 6 * (int64_t)min(j, N - 1);
+        if (z < deg && !(a.mir && (a.mir[pos] & kMirT))) fl |= 1;
+        if (i >= a.nown || j >= a.nown) fl |= 2;
+        const double *ej = op.e + 6 * (int64_t)min(j, N - 1);
         float4 *S = reinterpret_cast<float4 *>(SLT + (3 * z) * 64 + ll);
         S[0] = make_float4(__int_as_float(fl), (float)ej[0], (float)ej[1], (float)ej[2]);
         S[64] = make_float4((float)ej[3], (float)ej[4], (float)ej[5], 0.f);
-        S[128] = reinterpret_cast<const float4 *>(a2s)[pos];
+        S[128] = reinterpret_cast<const float4 *>(op.a2s)[pos];
     }
     __syncthreads();  // the only barrier: nothing below may wait for another wave
     // ---- compute: this wave's systems
     const int32_t i = 64 * s + l;
     if (i >= N) return;
-    const double2 e0 = E[l], e1 = E[64 + l], e2 = E[128 + l];
-    const double ei[6] = {e0.x, e0.y, e1.x, e1.y, e2.x, e2.y};
+    double ei[6];
+    ld_e(E, l, ei);
 #pragma unroll 1
     for (int trip = 0; trip < TRIPS; ++trip) {
         const int32_t b = chunk * PW + trip * W + wv;
         if (b >= B) break;
-        const double *I0b = geo.J0 + (int64_t)b * N, *I1b = geo.J1 + (int64_t)b * N;
-        const double hb = geo.dt[b];
+        const double *I0b = op.I0 + (int64_t)b * N, *I1b = a.J1 + (int64_t)b * N;
+        const double hb = a.dt[b];
         float G[WMAX][6];  // the slots' 3x3 a1 sums (symmetric: xx xy xz yy yz zz)
 #pragma unroll
         for (int z = 0; z < WMAX; ++z)
@@ -779,14 +785,14 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))) voi
         double f0 = 0.0, f1 = 0.0;
         const double Ii0 = I0b[i], pdi = (I1b[i] - Ii0) / hb;
         for (int32_t t = 0; t < wt; ++t) {
-            const double2 *P = INC + (7 * t) * 64 + l;
-            const int4 q = *reinterpret_cast<const int4 *>(P);
+            int4 q;
+            const double2 *P = ld_inc_rec<7>(INC, t, l, q);
             const double aj = I0b[q.z], ak = I0b[q.w], bj = I1b[q.z], bk = I1b[q.w];
-            const double2 g01 = P[1 * 64], g23 = P[2 * 64], g45 = P[3 * 64], g67 = P[4 * 64], g8a = P[5 * 64];
+            double g[9], At;
+            ld_inc_geo(P, g, At);
             const int4 ws = *reinterpret_cast<const int4 *>(P + 6 * 64);
-            const double g[9] = {g01.x, g01.y, g23.x, g23.y, g45.x, g45.y, g67.x, g67.y, g8a.x};
-            asm_inc_term<WMAX>(i, q.x < M, q.y, q.z, q.w, ws.y, g, g8a.y, __int_as_float(ws.x), ei, Ii0, pdi, aj, ak,
-                               bj, bk, hb, f0, f1, G);
+            asm_inc_term<WMAX>(i, q.x < M, q.y, q.z, q.w, ws.y, g, At, __int_as_float(ws.x), ei, Ii0, pdi, aj, ak, bj,
+                               bk, hb, f0, f1, G);
         }
         const int64_t vi = (int64_t)b * N + i;
         float eif[6];
@@ -803,8 +809,8 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(4))) voi
                     const float ej[6] = {s0.y, s0.z, s0.w, s1.x, s1.y, s1.z};
                     float acc[4];
                     g3_slot(G[z], eif, ej, acc);
-                    row_slot_store(acc, S[128], z == 0, (fl & 2) != 0, (int64_t)b * sell_nb + o + z * 64 + l, vi, f0,
-                                   f1, block_jacobi, A, dinv32, rhs, Ah);
+                    row_slot_store(acc, S[128], z == 0, (fl & 2) != 0, (int64_t)b * a.sell_nb + o + z * 64 + l, vi, f0,
+                                   f1, a);
                 }
             }
         }
@@ -1095,50 +1101,28 @@ void launch_assemble(mof_mesh *m, int32_t B, const double *I0, const double *I1,
     w.J0 = J0;
     w.J1 = J1;
     w.JB = B;
-    const TriGeo geo{m->gw.p, m->e.p, m->area.p, J0, J1, w.dt.p};
     const int64_t snb = m->pat.sell_nb();
     const dim3 gb(xcd_grid((int32_t)((snb + kWG - 1) / kWG), B, kGrpAsm));
     const int bj = block_jacobi ? 1 : 0;
     // multigrid: the level-0 smoother's bf16 operator comes from here
     AmgBf16 bf{nullptr};
     if (amg && precision == MOF_PREC_MIXED) bf = amg_bf16_targets(m, B);
-    const int32_t nblk_rows = (int32_t)((m->N + kRowsPerWG - 1) / kRowsPerWG);
-    const int32_t *mirw = m->sym_reads ? m->sell_mir.p : nullptr;
-#define MOF_ASM_RC_LAUNCH(WM)                                                                                     \
-    k_assemble_rows_rc<WM><<<xcd_grid(nblk_rows, B, kGrpAsm), kWG, 0, s>>>(                                        \
-        m->N, m->M, nblk_rows, B, snb, m->sell_off.p, m->sell_col.p, m->vptr.p, m->tsell_off.p,                    \
-        reinterpret_cast<const int4 *>(m->tinc.p), m->tslot.p, m->w12_32.p, m->a2s32.p, bj, w.A32.p, w.dinv32.p,   \
-        w.rhs.p, bf.A0h, m->n_own, mirw, geo)
-    if (rows && m->asm_lds) {
-        // the staged kernel (mesh_set_own: max_w <= 8 and the widest slice fits
-        // kAsmLdsCap). A small mesh or batch (fewer than kAsmLdsFill workgroups
-        // at kAsmLdsTrips systems per wave) takes one system per wave instead, so
-        // the launch still fills the CUs; a system's bits do not depend on the split
-        static LdsLimit limit;
-        const auto kern = &k_assemble_lds<kAsmLdsW, kAsmLdsTrips>, kern1 = &k_assemble_lds<kAsmLdsW, 1>;
-        raise_lds_limit(limit, m->device,
-                        {reinterpret_cast<const void *>(kern), reinterpret_cast<const void *>(kern1)}, kAsmLdsCap);
-        MOF_REQUIRE(W <= kAsmLdsMaxW && m->asm_lds_bytes <= kAsmLdsCap, "staged assembly: mesh not eligible");
-        const int32_t nsl = m->pat.nslices;
-        int32_t nchunk = (B + kAsmLdsW * kAsmLdsTrips - 1) / (kAsmLdsW * kAsmLdsTrips);
-        const bool one = (int64_t)nsl * nchunk < kAsmLdsFill && !g_force_assembly_trips.load();
-        if (one) nchunk = (B + kAsmLdsW - 1) / kAsmLdsW;
-        const unsigned grid = xcd_grid(nsl, nchunk, kGrpAsmLds);
-        MOF_REQUIRE((int64_t)grid * 64 * kAsmLdsW < ((int64_t)1 << 32), "launch grid past 2^32 work-items");
-        g_assembly_launches[one ? 1 : 2]++;
-        (one ? kern1 : kern)<<<dim3(grid), 64 * kAsmLdsW, (size_t)m->asm_lds_bytes, s>>>(
-            m->N, m->M, nsl, B, snb, m->sell_off.p, m->sell_col.p, m->vptr.p, m->tsell_off.p,
-            reinterpret_cast<const int4 *>(m->tinc.p), m->tslot.p, m->w12_32.p, m->a2s32.p, bj, w.A32.p, w.dinv32.p,
-            w.rhs.p, bf.A0h, m->n_own, mirw, geo);
-    } else if (rows && W <= 8) {
-        g_assembly_launches[0]++;
-        MOF_ASM_RC_LAUNCH(8);
-    } else if (rows) {
-        g_assembly_launches[0]++;
-        MOF_ASM_RC_LAUNCH(16);
-    }
-#undef MOF_ASM_RC_LAUNCH
-    else if (precision == MOF_PREC_MIXED)
+    if (rows) {
+        const AsmArgs a = asm_args(m, B, J0, J1, block_jacobi, bf.A0h);
+        const int32_t nblk_rows = (int32_t)((m->N + kRowsPerWG - 1) / kRowsPerWG);
+        if (m->asm_lds.used) {
+            // the staged kernel (mesh_set_own: kStagedAsm fits), launch_staged (mof_staged.h)
+            static LdsLimit limit;
+            launch_staged<kAsmLdsW, kAsmLdsTrips>(&k_assemble_lds<kAsmLdsW, kAsmLdsTrips>,
+                                                  &k_assemble_lds<kAsmLdsW, 1>, kAsmLdsFill, kGrpAsmLds, B, m,
+                                                  kStagedAsm, m->asm_lds, g_staged_asm, limit, s, a,
+                                                  (int32_t)m->pat.nslices);
+        } else {
+            g_staged_asm.launches[0]++;
+            const auto kern = W <= 8 ? &k_assemble_rows_rc<8> : &k_assemble_rows_rc<16>;
+            kern<<<dim3(xcd_grid(nblk_rows, B, kGrpAsm)), kWG, 0, s>>>(a, nblk_rows);
+        }
+    } else if (precision == MOF_PREC_MIXED)
         k_assemble_mixed<<<gb, kWG, 0, s>>>(snb, m->N, m->M, B, m->sell_blk.p, m->blk_row.p, m->vcol.p,
                                             m->cptr.p, m->clist.p, m->w12_32.p, m->a2s32.p, w.u32.p,
                                             w.fc.p, bj, w.A32.p, w.dinv32.p, w.rhs.p, bf.A0h, m->n_own);

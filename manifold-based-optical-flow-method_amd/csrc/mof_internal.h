@@ -156,48 +156,48 @@ std::vector<int32_t> sell_mirror(const Pattern &pat, int32_t nown, int sym, bool
 std::vector<uint32_t> sell_index_pack(const Pattern &pat, const std::vector<int32_t> &mir);
 // tests only (mof_test_force_index32): every mesh set up from now on keeps the 32-bit tables
 extern std::atomic<int> g_force_index32;
-// The staged fp64 residual (k_residual_lds, mof_pcg.hip) keeps the geometry
-// all systems share of one 64-row slice in LDS: per row 36 B per a2 slot
-// (column + fp64 block), 192 B per incidence slot (tinc record, 9 hat
-// gradients, two vertices' tangent bases, A_T / 12) and 48 B (its own bases).
-// A mesh (or decomposed part) takes the kernel when its widest slice fits
-// kResLdsCap, the fixed dynamic-LDS limit the kernel is given; the decision
-// depends on the pattern alone, never on the batch.
-constexpr int64_t kResLdsCap = 160 * 1024;
-inline int64_t res_slice_bytes(int32_t w_a2, int32_t w_inc) {
-    return (int64_t)kSlice * ((int64_t)w_a2 * 36 + (int64_t)w_inc * 192 + 48);
-}
-int64_t res_staged_bytes(const Pattern &pat);  // the maximum over the slices
-// tests only (mof_test_force_residual_rows): every mesh set up from now on keeps k_residual_rcn
-extern std::atomic<int> g_force_residual_rows;
-// tests only (mof_test_force_residual_trips): the staged kernel's multi-trip instance whatever the
-// launch's size (launch_residual_lds otherwise gives small launches one pair per wave)
-extern std::atomic<int> g_force_residual_trips;
-// launches so far of k_residual_rcn, the one-trip and the multi-trip k_residual_lds (mof_test_residual_launches)
-extern std::atomic<int64_t> g_residual_launches[3];
-// The staged row assembly (k_assemble_lds, mof_assemble.hip) keeps, of one
-// 64-row slice, what every system reads alike in LDS: per row 112 B per
+// A staged row path keeps, of one 64-row SELL slice, what every system reads
+// alike in LDS; StagedKind is its size rule (bytes per row; the planes:
+// mof_staged.h). A mesh (or decomposed part) takes the staged kernel when its
+// widest row fits max_w and its widest slice fits lds_cap, the fixed dynamic-LDS
+// limit the kernel is given; the pattern alone decides, never the batch.
+struct StagedKind {
+    int32_t a2_bytes, inc_bytes, fixed_bytes;  // per a2 slot, per incidence slot, per row
+    int64_t lds_cap;
+    int32_t max_w;  // widest row (blocks) the kernel takes; 0: any
+};
+// The fp64 residual (k_residual_lds, mof_pcg.hip): 36 B per a2 slot (column +
+// fp64 block), 192 B per incidence slot (tinc record, 9 hat gradients, two
+// vertices' tangent bases, A_T / 12) and 48 B (the row's own bases).
+constexpr StagedKind kStagedRes{36, 192, 48, 160 * 1024, 0};
+// The row assembly (k_assemble_lds, mof_assemble.hip): 48 B per a2 slot (flags,
+// e_j as floats, the fp32 lambda a2 block; three 16-byte planes), 112 B per
 // incidence slot (tinc record, 9 hat gradients, A_T, A_T / 12 as float, tslot;
-// seven 16-byte planes), 48 B per a2 slot (flags, e_j as floats, the fp32
-// lambda a2 block; three planes) and 48 B (its own bases). A mesh (or
-// decomposed part) takes the kernel when its widest row fits the 8 register
-// slots of k_assemble_rows_rc<8> and its widest slice fits kAsmLdsCap, the
-// fixed dynamic-LDS limit the kernel is given; the pattern alone decides.
-constexpr int64_t kAsmLdsCap = 160 * 1024;
-constexpr int32_t kAsmLdsMaxW = 8;
-inline int64_t asm_slice_bytes(int32_t w_a2, int32_t w_inc) {
-    return (int64_t)kSlice * ((int64_t)w_inc * 112 + (int64_t)w_a2 * 48 + 48);
+// seven planes) and 48 B; rows up to the 8 register slots of k_assemble_rows_rc<8>.
+constexpr StagedKind kStagedAsm{48, 112, 48, 160 * 1024, 8};
+inline int64_t staged_slice_bytes(const StagedKind &k, int32_t w_a2, int32_t w_inc) {
+    return (int64_t)kSlice * ((int64_t)w_a2 * k.a2_bytes + (int64_t)w_inc * k.inc_bytes + k.fixed_bytes);
 }
-int64_t asm_staged_bytes(const Pattern &pat);  // the maximum over the slices
-inline bool asm_staged_fits(const Pattern &pat) {
-    return pat.max_w <= kAsmLdsMaxW && asm_staged_bytes(pat) <= kAsmLdsCap;
+int64_t staged_bytes(const Pattern &pat, const StagedKind &k);  // the maximum over the slices
+inline bool staged_fits(const Pattern &pat, const StagedKind &k) {
+    return (k.max_w == 0 || pat.max_w <= k.max_w) && staged_bytes(pat, k) <= k.lds_cap;
 }
-// tests only (mof_test_force_assembly_rows): every mesh set up from now on keeps k_assemble_rows_rc
-extern std::atomic<int> g_force_assembly_rows;
-// tests only (mof_test_force_assembly_trips): the staged assembly's multi-trip instance whatever the launch's size
-extern std::atomic<int> g_force_assembly_trips;
-// launches so far of k_assemble_rows_rc, the one-trip and the multi-trip k_assemble_lds (mof_test_assembly_launches)
-extern std::atomic<int64_t> g_assembly_launches[3];
+// A mesh's state of one kind (mesh_set_own): its widest slice's bytes; the handle takes the staged kernel
+struct StagedState {
+    int64_t bytes = 0;
+    bool used = false;
+};
+// Tests only, per kind (mof_test_force_{residual,assembly}_rows / _trips,
+// mof_test_{residual,assembly}_launches): force_rows -- every mesh set up from
+// now on keeps the row kernel (k_residual_rcn / k_assemble_rows_rc);
+// force_trips -- the multi-trip instance whatever the launch's size
+// (launch_staged otherwise gives small launches one trip per wave); launches
+// so far of the row kernel, the one-trip and the multi-trip staged kernel.
+struct StagedHooks {
+    std::atomic<int> force_rows{0}, force_trips{0};
+    std::atomic<int64_t> launches[3]{};
+};
+extern StagedHooks g_staged_res, g_staged_asm;
 
 // A kernel's dynamic-LDS limit, raised once per process and device to a fixed
 // cap -- never to one mesh's own size, which a later mesh would lower under an
@@ -340,12 +340,9 @@ struct mof_mesh {
     // kernels keep the 32-bit tables
     mof::DevArray<uint32_t> sell_idx;
     bool idx_packed = false;
-    // the re-forming fp64 residual runs staged in LDS (res_staged_bytes <= kResLdsCap)
-    int64_t res_lds_bytes = 0;
-    bool res_lds = false;
-    // the mixed-precision row assembly runs staged in LDS (asm_staged_fits)
-    int64_t asm_lds_bytes = 0;
-    bool asm_lds = false;
+    // the re-forming fp64 residual (kStagedRes) and the mixed-precision row
+    // assembly (kStagedAsm) run staged in LDS
+    mof::StagedState res_lds, asm_lds;
     mof::DevArray<double> e, gw, iw, area, a2;  // a2: [sell_nb][4] (unscaled, bit-exact)
     // operator copies: lambda*a2 (cached per lambda) and A_T/12 with a zero slot M
     mof::DevArray<double> a2s64, w12_64;

@@ -270,19 +270,11 @@ std::vector<uint32_t> sell_index_pack(const Pattern &pat, const std::vector<int3
     return out;
 }
 
-int64_t res_staged_bytes(const Pattern &pat) {
+int64_t staged_bytes(const Pattern &pat, const StagedKind &k) {
     int64_t mx = 0;
     for (int32_t s = 0; s < pat.nslices; ++s)
-        mx = std::max(mx, res_slice_bytes((pat.sell_off[s + 1] - pat.sell_off[s]) / kSlice,
-                                          (pat.tsell_off[s + 1] - pat.tsell_off[s]) / kSlice));
-    return mx;
-}
-
-int64_t asm_staged_bytes(const Pattern &pat) {
-    int64_t mx = 0;
-    for (int32_t s = 0; s < pat.nslices; ++s)
-        mx = std::max(mx, asm_slice_bytes((pat.sell_off[s + 1] - pat.sell_off[s]) / kSlice,
-                                          (pat.tsell_off[s + 1] - pat.tsell_off[s]) / kSlice));
+        mx = std::max(mx, staged_slice_bytes(k, (pat.sell_off[s + 1] - pat.sell_off[s]) / kSlice,
+                                             (pat.tsell_off[s + 1] - pat.tsell_off[s]) / kSlice));
     return mx;
 }
 

@@ -48,6 +48,7 @@
 #include "mof_dd.h"
 #include "mof_internal.h"
 #include "mof_rowkern.h"
+#include "mof_staged.h"
 
 namespace mof {
 
@@ -61,22 +62,6 @@ enum { kPcRedPq = 16, kPcRedRzrr, kPcUpdate, kPcConvEarly, kPcOuterUpdate, kPcOu
 std::atomic<int64_t> g_pcg_launches[kPcKernels];
 
 namespace {
-
-// The operator of B systems sharing a mesh.
-template <typename V>
-struct OpArgs {
-    int32_t N, M;
-    const int32_t *sell_off, *sell_col;  // a2 blocks, SELL-64
-    const V *a2s;                        // [sell_nb][4] lambda * a2
-    const int32_t *tsell_off;            // vertex -> incident triangles, SELL-64
-    const int4 *tinc;                    // {T, corner, vertex of corner+1, vertex of corner+2}
-    const V *w12;                        // [M+1] A_T / 12 (slot M = 0)
-    const V *u;                          // [B][M+1][6] u_T per system (slot M = 0), or null:
-    // u re-formed from the timestep's I row as k_tri_step forms it
-    const double *gw, *e;                // [M][9] hat gradients, [N][6] tangent bases
-    const double *I0;                    // [B][ldI] I_k rows (internal order)
-    int64_t ldI;
-};
 
 template <typename V>
 struct PcgArgs {
@@ -995,6 +980,20 @@ __device__ __forceinline__ void rcn_out(int64_t vi, bool own, bool act, const do
         ff += f.x * f.x + f.y * f.y;
     }
 }
+// Pair bp's systems (the last pair of an odd batch repeats system B - 1) and
+// which of them are live; false: none is.
+template <int NS>
+__device__ __forceinline__ bool res_pair(int32_t bp, int32_t B, const int32_t *__restrict__ sysi, int32_t (&bs)[NS],
+                                         bool (&act)[NS]) {
+    bool any = false;
+#pragma unroll
+    for (int t = 0; t < NS; ++t) {
+        bs[t] = min(NS * bp + t, B - 1);
+        act[t] = NS * bp + t < B && sysi[bs[t] * kSysStride + SI_ACTIVE] != 0;
+        any |= act[t];
+    }
+    return any;
+}
 template <int NS>
 __global__ __launch_bounds__(kWG) void k_residual_rcn(OpArgs<double> op, int32_t nblk, int32_t B, RedArgs rd,
                                                       const double *__restrict__ rhs,
@@ -1006,14 +1005,8 @@ __global__ __launch_bounds__(kWG) void k_residual_rcn(OpArgs<double> op, int32_t
     int32_t rb, bp;
     if (!xcd_map(nblk, (B + NS - 1) / NS, rb, bp, kGrpRes)) return;
     int32_t bs[NS];
-    bool act[NS], any = false;
-#pragma unroll
-    for (int t = 0; t < NS; ++t) {
-        bs[t] = min(NS * bp + t, B - 1);
-        act[t] = NS * bp + t < B && sysi[bs[t] * kSysStride + SI_ACTIVE] != 0;
-        any |= act[t];
-    }
-    if (!any) return;
+    bool act[NS];
+    if (!res_pair<NS>(bp, B, sysi, bs, act)) return;
     const int32_t N = op.N;
     double v[2 * NS];  // rr, ff of each system
 #pragma unroll
@@ -1057,9 +1050,10 @@ __global__ __launch_bounds__(kWG) void k_residual_rcn(OpArgs<double> op, int32_t
 // block_sum's order.
 //
 // Staged bytes of a slice of wa a2 slots and wt incidence slots (double2
-// units; res_staged_bytes, mof_pattern.cpp): E 3 planes, BLK 2 wa, INC 12 wt
+// units; kStagedRes, mof_internal.h): E 3 planes, BLK 2 wa, INC 12 wt
 // {tinc | g0 g1 | g2 g3 | g4 g5 | g6 g7 | g8 w12 | ej x3 | ek x3}, then the wa
-// 4-byte column planes.
+// 4-byte column planes. E and an incidence slot's first six planes are the
+// ones the staged assembly has too (stage_e, stage_inc_geo, mof_staged.h).
 //
 // 16 waves x 4 trips (C3, 1536 systems: 10.27 / 9.15 / 8.78 ms per launch at
 // 1 / 2 / 4 trips -- one workgroup per CU, so staging is not hidden and more
@@ -1068,10 +1062,10 @@ __global__ __launch_bounds__(kWG) void k_residual_rcn(OpArgs<double> op, int32_t
 // before the first use, but one incidence's at a time: two per load batch
 // need 68 B of scratch per lane at the 128 VGPRs a 1024-thread workgroup
 // leaves a wave (110 and none as written, the trip loop not unrolled).
-constexpr int kLdsW = 16, kLdsTrips = 4;
-constexpr int kLdsUA = 4;  // a2 slots per load batch
+constexpr int kResLdsW = 16, kResLdsTrips = 4;
+constexpr int kResLdsUA = 4;  // a2 slots per load batch
 constexpr int32_t kGrpResLds = 1;  // an XCD walks consecutive slices of one pair chunk
-constexpr int64_t kLdsFill = 1024;  // workgroups (4 per CU) below which a launch takes one trip per wave
+constexpr int64_t kResLdsFill = 1024;  // workgroups (4 per CU) below which a launch takes one trip per wave
 template <int NS, int W, int TRIPS>
 __global__ __launch_bounds__(64 * W) void k_residual_lds(OpArgs<double> op, int32_t nsl, int32_t B, RedArgs rd,
                                                          const double *__restrict__ rhs,
@@ -1096,8 +1090,7 @@ __global__ __launch_bounds__(64 * W) void k_residual_lds(OpArgs<double> op, int3
         if (__ballot(any) == 0) return;
     }
     const int32_t N = op.N;
-    const int32_t o = op.sell_off[s], wa = (op.sell_off[s + 1] - o) >> 6;
-    const int32_t to = op.tsell_off[s], wt = (op.tsell_off[s + 1] - to) >> 6;
+    const auto [o, wa, to, wt] = slice_view(op.sell_off, op.tsell_off, s);
     double2 *const E = sm, *const BLK = sm + 3 * 64, *const INC = BLK + 2 * 64 * wa;
     int32_t *const COL = reinterpret_cast<int32_t *>(INC + 12 * 64 * wt);
     // ---- staging (all NT threads; lanes past N - 1 of the last slice stage
@@ -1109,25 +1102,12 @@ __global__ __launch_bounds__(64 * W) void k_residual_lds(OpArgs<double> op, int3
         BLK[(2 * t) * 64 + ll] = bp[0];
         BLK[(2 * t + 1) * 64 + ll] = bp[1];
     }
-    for (int32_t q = threadIdx.x; q < 3 * 64; q += NT) {
-        const int32_t k = q >> 6, ll = q & 63;
-        E[q] = ld2(op.e + 6 * (int64_t)min(64 * s + ll, N - 1) + 2 * k);
-    }
+    stage_e<NT>(E, op.e, s, N);
     for (int32_t q = threadIdx.x; q < wt * 4 * 64; q += NT) {
         const int32_t ll = q & 63, part = (q >> 6) & 3, t = q >> 8;
         const int4 e = op.tinc[(int64_t)to + t * 64 + ll];
-        double2 *P = INC + (12 * t) * 64 + ll;
-        if (part == 0) {
-            const double *g = op.gw + 9 * (int64_t)min(e.x, op.M - 1);
-            *reinterpret_cast<int4 *>(P) = e;
-            P[1 * 64] = make_double2(g[0], g[1]);
-            P[2 * 64] = make_double2(g[2], g[3]);
-            P[3 * 64] = make_double2(g[4], g[5]);
-        } else if (part == 1) {
-            const double *g = op.gw + 9 * (int64_t)min(e.x, op.M - 1);
-            P[4 * 64] = make_double2(g[6], g[7]);
-            P[5 * 64] = make_double2(g[8], op.w12[e.x]);
-        } else {
+        double2 *P = stage_inc_geo<12>(INC, t, ll, part, e, op.gw, op.M, op.w12, e.x);
+        if (part >= 2) {
             const double *ev = op.e + 6 * (int64_t)(part == 2 ? e.z : e.w);
             double2 *Q = P + (part == 2 ? 6 : 9) * 64;
             Q[0] = ld2(ev);
@@ -1143,14 +1123,8 @@ __global__ __launch_bounds__(64 * W) void k_residual_lds(OpArgs<double> op, int3
         const int32_t bp = chunk * PW + trip * W + wv;
         if (bp >= npair) break;
         int32_t bs[NS];
-        bool act[NS], any = false;
-#pragma unroll
-        for (int t = 0; t < NS; ++t) {
-            bs[t] = min(NS * bp + t, B - 1);
-            act[t] = NS * bp + t < B && sysi[bs[t] * kSysStride + SI_ACTIVE] != 0;
-            any |= act[t];
-        }
-        if (!any) continue;
+        bool act[NS];
+        if (!res_pair<NS>(bp, B, sysi, bs, act)) continue;
         double v[2 * NS];  // rr, ff of each system
 #pragma unroll
         for (int t = 0; t < 2 * NS; ++t) v[t] = 0.0;
@@ -1159,16 +1133,16 @@ __global__ __launch_bounds__(64 * W) void k_residual_lds(OpArgs<double> op, int3
 #pragma unroll
             for (int t = 0; t < NS; ++t) acc[t][0] = acc[t][1] = 0.0;
             // lambda a2 x, slots in order
-            for (int32_t t0 = 0; t0 < wa; t0 += kLdsUA) {
-                double2 xj[kLdsUA][NS];
+            for (int32_t t0 = 0; t0 < wa; t0 += kResLdsUA) {
+                double2 xj[kResLdsUA][NS];
 #pragma unroll
-                for (int u = 0; u < kLdsUA; ++u) {
+                for (int u = 0; u < kResLdsUA; ++u) {
                     const int32_t j = COL[min(t0 + u, wa - 1) * 64 + l];
 #pragma unroll
                     for (int t = 0; t < NS; ++t) xj[u][t] = ld2(x64 + 2 * ((int64_t)bs[t] * N + j));
                 }
 #pragma unroll
-                for (int u = 0; u < kLdsUA; ++u) {
+                for (int u = 0; u < kResLdsUA; ++u) {
                     const int32_t tt = min(t0 + u, wa - 1);
                     const double2 b0 = BLK[(2 * tt) * 64 + l], b1 = BLK[(2 * tt + 1) * 64 + l];
                     const double blk[4] = {b0.x, b0.y, b1.x, b1.y};
@@ -1184,12 +1158,12 @@ __global__ __launch_bounds__(64 * W) void k_residual_lds(OpArgs<double> op, int3
                 xi[t] = ld2(x64 + 2 * ((int64_t)bs[t] * N + i));
                 Ii[t] = op.I0[(int64_t)bs[t] * op.ldI + i];
             }
-            const double2 e0 = E[l], e1 = E[64 + l], e2 = E[128 + l];
-            const double ei[6] = {e0.x, e0.y, e1.x, e1.y, e2.x, e2.y};
+            double ei[6];
+            ld_e(E, l, ei);
             // the incident triangles in order
             for (int32_t t0 = 0; t0 < wt; ++t0) {
-                const double2 *P = INC + (12 * t0) * 64 + l;
-                const int4 q = *reinterpret_cast<const int4 *>(P);
+                int4 q;
+                const double2 *P = ld_inc_rec<12>(INC, t0, l, q);
                 double Ij[NS], Ik[NS];
                 double2 xj[NS], xk[NS];
 #pragma unroll
@@ -1201,16 +1175,16 @@ __global__ __launch_bounds__(64 * W) void k_residual_lds(OpArgs<double> op, int3
                     xj[t] = ld2(x64 + 2 * (vb + q.z));
                     xk[t] = ld2(x64 + 2 * (vb + q.w));
                 }
-                const double2 g01 = P[64], g23 = P[2 * 64], g45 = P[3 * 64], g67 = P[4 * 64], g8w = P[5 * 64];
+                double g[9], w12;
+                ld_inc_geo(P, g, w12);
                 const double2 j0 = P[6 * 64], j1 = P[7 * 64], j2 = P[8 * 64];
                 const double2 k0 = P[9 * 64], k1 = P[10 * 64], k2 = P[11 * 64];
-                const double g[9] = {g01.x, g01.y, g23.x, g23.y, g45.x, g45.y, g67.x, g67.y, g8w.x};
                 const double ej[6] = {j0.x, j0.y, j1.x, j1.y, j2.x, j2.y};
                 const double ek[6] = {k0.x, k0.y, k1.x, k1.y, k2.x, k2.y};
 #pragma unroll
                 for (int t = 0; t < NS; ++t) {
                     double val[2];
-                    rcn_tri_term(q.y, g, ei, ej, ek, g8w.y, Ii[t], Ij[t], Ik[t], xi[t], xj[t], xk[t], val);
+                    rcn_tri_term(q.y, g, ei, ej, ek, w12, Ii[t], Ij[t], Ik[t], xi[t], xj[t], xk[t], val);
                     acc[t][0] += val[0];
                     acc[t][1] += val[1];
                 }
@@ -1370,25 +1344,6 @@ __global__ void k_fail_running(int32_t B, int32_t it, int32_t *__restrict__ sysi
     }
 }
 
-template <typename V>
-OpArgs<V> make_op(mof_mesh *m, const V *a2s, const V *w12, const V *u) {
-    OpArgs<V> op;
-    op.N = m->N;
-    op.M = m->M;
-    op.sell_off = m->sell_off.p;
-    op.sell_col = m->sell_col.p;
-    op.a2s = a2s;
-    op.tsell_off = m->tsell_off.p;
-    op.tinc = reinterpret_cast<const int4 *>(m->tinc.p);
-    op.w12 = w12;
-    op.u = u;
-    op.gw = m->gw.p;
-    op.e = m->e.p;
-    op.I0 = m->ws.J0;
-    op.ldI = m->N;
-    return op;
-}
-
 // u64 of the batch, or null when the mixed path left it unwritten (the
 // residual then re-forms u from the batch's I rows)
 OpArgs<double> op64(mof_mesh *m) {
@@ -1408,31 +1363,18 @@ MatArgs<V> make_mat(mof_mesh *m, const V *A) {
     return mt;
 }
 
-// The staged residual of a mesh whose widest slice fits kResLdsCap
-// (mesh_set_own): k_residual_lds into the per-slice records, then the fold.
-// The kernel's dynamic-LDS limit is raised once per process and device to
-// the fixed cap, never to a mesh's own size (a later, wider mesh would
-// otherwise launch past the limit an earlier one set).
+// The staged residual of a mesh whose widest slice fits kStagedRes
+// (mesh_set_own): k_residual_lds into the per-slice records (launch_staged,
+// mof_staged.h), then the fold.
 void launch_residual_lds(mof_mesh *m, const OpArgs<double> &op, int32_t nblk, int32_t B, hipStream_t s, RedArgs rd,
                          const double *rhs, const double *x64, const int32_t *sysi, double *r64, double *part) {
     static LdsLimit limit;
-    const auto kern = &k_residual_lds<kResNS, kLdsW, kLdsTrips>, kern1 = &k_residual_lds<kResNS, kLdsW, 1>;
-    raise_lds_limit(limit, m->device, {reinterpret_cast<const void *>(kern), reinterpret_cast<const void *>(kern1)},
-                    kResLdsCap);
-    const int32_t nsl = m->pat.nslices, npair = (B + kResNS - 1) / kResNS;
-    // a small mesh or batch (fewer than kLdsFill workgroups at kLdsTrips pairs
-    // per wave) takes one pair per wave instead, so the launch still fills
-    // the CUs; a system's bits do not depend on the split
-    int32_t nchunk = (npair + kLdsW * kLdsTrips - 1) / (kLdsW * kLdsTrips);
-    const bool one = (int64_t)nsl * nchunk < kLdsFill && !g_force_residual_trips.load();
-    if (one) nchunk = (npair + kLdsW - 1) / kLdsW;
-    MOF_REQUIRE(m->res_lds_bytes <= kResLdsCap && m->ws.res_spart.n >= (size_t)2 * nsl * B,
-                "staged residual: workspace not set up");
-    const unsigned grid = xcd_grid(nsl, nchunk, kGrpResLds);
-    MOF_REQUIRE((int64_t)grid * 64 * kLdsW < ((int64_t)1 << 32), "launch grid past 2^32 work-items");
-    g_residual_launches[one ? 1 : 2]++;
-    (one ? kern1 : kern)<<<dim3(grid), 64 * kLdsW, (size_t)m->res_lds_bytes, s>>>(op, nsl, B, rd, rhs, x64, sysi, r64,
-                                                                                   m->ws.res_spart.p);
+    const int32_t nsl = m->pat.nslices;
+    MOF_REQUIRE(m->ws.res_spart.n >= (size_t)2 * nsl * B, "staged residual: workspace not set up");
+    launch_staged<kResLdsW, kResLdsTrips>(&k_residual_lds<kResNS, kResLdsW, kResLdsTrips>,
+                                          &k_residual_lds<kResNS, kResLdsW, 1>, kResLdsFill, kGrpResLds,
+                                          (B + kResNS - 1) / kResNS, m, kStagedRes, m->res_lds, g_staged_res, limit, s,
+                                          op, nsl, B, rd, rhs, x64, sysi, r64, m->ws.res_spart.p);
     const int64_t nrec = (int64_t)B * nblk;
     k_residual_fold<<<dim3((unsigned)((nrec + kWG - 1) / kWG)), kWG, 0, s>>>(nsl, nblk, B, rd, sysi,
                                                                              m->ws.res_spart.p, part);
@@ -1450,10 +1392,10 @@ void launch_residual(mof_mesh *m, int32_t nblk, int32_t B, hipStream_t s, RedArg
     const OpArgs<double> op = op64(m);
     if (op.u)
         k_residual<<<dim3(xcd_grid(nblk, B, kGrpRes)), kWG, 0, s>>>(op, nblk, B, rd, args...);
-    else if (m->res_lds)
+    else if (m->res_lds.used)
         launch_residual_lds(m, op, nblk, B, s, rd, args...);
     else {
-        g_residual_launches[0]++;
+        g_staged_res.launches[0]++;
         k_residual_rcn<kResNS><<<dim3(xcd_grid(nblk, (B + kResNS - 1) / kResNS, kGrpRes)), kWG, 0, s>>>(
             op, nblk, B, rd, args...);
     }
@@ -2206,7 +2148,7 @@ void ensure_workspace(mof_mesh *m, int32_t B, uint32_t precision) {
     w.sc.alloc((size_t)6 * B);
     w.sc.zero(m->stream);
     w.part_rr0.alloc((size_t)2 * w.nblk * B);
-    if (m->res_lds) w.res_spart.alloc((size_t)2 * m->pat.nslices * B);
+    if (m->res_lds.used) w.res_spart.alloc((size_t)2 * m->pat.nslices * B);
     w.part_dx.alloc((size_t)2 * ((N + kWG - 1) / kWG) * B);
     w.sysd.alloc((size_t)kSysStride * B);
     w.sysi.alloc((size_t)kSysStride * B);

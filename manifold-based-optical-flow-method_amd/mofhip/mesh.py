@@ -318,17 +318,36 @@ def index_probe(triangles, n_vertices: int, sym: int = -1, reorder: bool = True)
             "packed_used": bool(pu.value)}
 
 
-class force_index32:
-    """Tests only (mof_test_force_index32): handles created inside the block
-    keep the two 32-bit index tables where the packed words would fit."""
+class _Hook:
+    """A tests-only switch of the library, on inside the block (``_name``: its entry point)."""
 
     def __enter__(self):
-        L.check(L.lib().mof_test_force_index32(1))
+        L.check(getattr(L.lib(), self._name)(1))
         return self
 
     def __exit__(self, *exc):
-        L.check(L.lib().mof_test_force_index32(0))
+        L.check(getattr(L.lib(), self._name)(0))
         return False
+
+
+class force_index32(_Hook):
+    """Tests only (mof_test_force_index32): handles created inside the block
+    keep the two 32-bit index tables where the packed words would fit."""
+    _name = "mof_test_force_index32"
+
+
+def _staged_probe(name: str, triangles, n_vertices: int, reorder: bool) -> dict:
+    T = np.ascontiguousarray(triangles, dtype=np.int32)
+    flags = 0 if reorder else L.MOF_NO_REORDER
+    nb, used = ctypes.c_int64(0), ctypes.c_int32(0)
+    L.check(getattr(L.lib(), name)(L.ptr(T), int(n_vertices), len(T), flags, ctypes.byref(nb), ctypes.byref(used)))
+    return {"staged_bytes": int(nb.value), "staged_used": bool(used.value)}
+
+
+def _staged_launches(name: str) -> dict:
+    c = np.zeros(3, dtype=np.int64)
+    L.check(getattr(L.lib(), name)(L.ptr(c)))
+    return {"rows": int(c[0]), "staged_one": int(c[1]), "staged_multi": int(c[2])}
 
 
 def residual_probe(triangles, n_vertices: int, reorder: bool = True) -> dict:
@@ -338,47 +357,26 @@ def residual_probe(triangles, n_vertices: int, reorder: bool = True) -> dict:
     48) bytes -- and ``staged_used``, whether a handle of the mesh takes that
     kernel (the bytes fit the kernel's fixed LDS limit). The batch plays no
     part."""
-    T = np.ascontiguousarray(triangles, dtype=np.int32)
-    flags = 0 if reorder else L.MOF_NO_REORDER
-    nb, used = ctypes.c_int64(0), ctypes.c_int32(0)
-    L.check(L.lib().mof_residual_probe(L.ptr(T), int(n_vertices), len(T), flags, ctypes.byref(nb),
-                                       ctypes.byref(used)))
-    return {"staged_bytes": int(nb.value), "staged_used": bool(used.value)}
+    return _staged_probe("mof_residual_probe", triangles, n_vertices, reorder)
 
 
-class force_residual_rows:
+class force_residual_rows(_Hook):
     """Tests only (mof_test_force_residual_rows): handles created inside the
     block keep the row kernel k_residual_rcn where the staged one would fit."""
-
-    def __enter__(self):
-        L.check(L.lib().mof_test_force_residual_rows(1))
-        return self
-
-    def __exit__(self, *exc):
-        L.check(L.lib().mof_test_force_residual_rows(0))
-        return False
+    _name = "mof_test_force_residual_rows"
 
 
-class force_residual_trips:
+class force_residual_trips(_Hook):
     """Tests only (mof_test_force_residual_trips): every staged residual launch
     inside the block takes the four-trip kernel of the large launches."""
-
-    def __enter__(self):
-        L.check(L.lib().mof_test_force_residual_trips(1))
-        return self
-
-    def __exit__(self, *exc):
-        L.check(L.lib().mof_test_force_residual_trips(0))
-        return False
+    _name = "mof_test_force_residual_trips"
 
 
 def residual_launches() -> dict:
     """Tests only (mof_test_residual_launches): launches so far in this process
     of the fp64 residual's row kernel (``rows``) and of the staged kernel with
     one (``staged_one``) and four (``staged_multi``) trips per wave."""
-    c = np.zeros(3, dtype=np.int64)
-    L.check(L.lib().mof_test_residual_launches(L.ptr(c)))
-    return {"rows": int(c[0]), "staged_one": int(c[1]), "staged_multi": int(c[2])}
+    return _staged_launches("mof_test_residual_launches")
 
 
 def assembly_probe(triangles, n_vertices: int, reorder: bool = True) -> dict:
@@ -388,47 +386,26 @@ def assembly_probe(triangles, n_vertices: int, reorder: bool = True) -> dict:
     and ``staged_used``, whether a handle of the mesh takes that kernel (no
     row wider than 8 blocks and the bytes fit the kernel's fixed LDS limit).
     The batch plays no part."""
-    T = np.ascontiguousarray(triangles, dtype=np.int32)
-    flags = 0 if reorder else L.MOF_NO_REORDER
-    nb, used = ctypes.c_int64(0), ctypes.c_int32(0)
-    L.check(L.lib().mof_assembly_probe(L.ptr(T), int(n_vertices), len(T), flags, ctypes.byref(nb),
-                                       ctypes.byref(used)))
-    return {"staged_bytes": int(nb.value), "staged_used": bool(used.value)}
+    return _staged_probe("mof_assembly_probe", triangles, n_vertices, reorder)
 
 
-class force_assembly_rows:
+class force_assembly_rows(_Hook):
     """Tests only (mof_test_force_assembly_rows): handles created inside the
     block keep the row kernel k_assemble_rows_rc where the staged one would fit."""
-
-    def __enter__(self):
-        L.check(L.lib().mof_test_force_assembly_rows(1))
-        return self
-
-    def __exit__(self, *exc):
-        L.check(L.lib().mof_test_force_assembly_rows(0))
-        return False
+    _name = "mof_test_force_assembly_rows"
 
 
-class force_assembly_trips:
+class force_assembly_trips(_Hook):
     """Tests only (mof_test_force_assembly_trips): every staged assembly launch
     inside the block takes the multi-trip kernel of the large launches."""
-
-    def __enter__(self):
-        L.check(L.lib().mof_test_force_assembly_trips(1))
-        return self
-
-    def __exit__(self, *exc):
-        L.check(L.lib().mof_test_force_assembly_trips(0))
-        return False
+    _name = "mof_test_force_assembly_trips"
 
 
 def assembly_launches() -> dict:
     """Tests only (mof_test_assembly_launches): launches so far in this process
     of the row assembly kernel (``rows``) and of the staged kernel with one
     (``staged_one``) and several (``staged_multi``) trips per wave."""
-    c = np.zeros(3, dtype=np.int64)
-    L.check(L.lib().mof_test_assembly_launches(L.ptr(c)))
-    return {"rows": int(c[0]), "staged_one": int(c[1]), "staged_multi": int(c[2])}
+    return _staged_launches("mof_test_assembly_launches")
 
 
 def assembly_readback(mesh: "DeviceMesh", system: int, device=None) -> dict:

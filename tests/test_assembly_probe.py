@@ -1,6 +1,6 @@
 """The size function that decides, per mesh, whether the mixed-precision row
 assembly runs with a row slice's geometry staged in LDS (k_assemble_lds) or as
-the row kernel (csrc/mof_pattern.cpp asm_staged_bytes), on the CPU through the
+the row kernel (csrc/mof_pattern.cpp staged_bytes, kStagedAsm), on the CPU through the
 host-only mof_assembly_probe: a 64-row slice of t incidence slots and w a2
 slots stages 64 (112 t + 48 w + 48) bytes, and the mesh takes the staged
 kernel when no row is wider than the kernel's 8 register slots and its widest

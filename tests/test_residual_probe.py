@@ -1,6 +1,6 @@
 """The size function that decides, per mesh, whether the fp64 residual runs
 with a row slice's geometry staged in LDS (k_residual_lds) or as the row
-kernel (csrc/mof_pattern.cpp res_staged_bytes), on the CPU through the
+kernel (csrc/mof_pattern.cpp staged_bytes, kStagedRes), on the CPU through the
 host-only mof_residual_probe: a 64-row slice of w a2 slots and t incidence
 slots stages 64 (36 w + 192 t + 48) bytes, and the mesh takes the staged
 kernel when its widest slice fits the kernel's fixed 160 KiB. That the
